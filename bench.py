@@ -35,7 +35,11 @@ Every part of it is measured in this run, none extrapolated:
              #2 FeedForward (TfFeedForward-style MLP) trial on 1 GPU (N = 1 only);
              #1 SkDt random-search trials on the CPU (N = 1 only).
 
-``python bench.py`` defaults to 1 GPU and finishes in a few minutes.
+A plain run (``python bench.py --gpus 1 --steps K --warmup W``) does phase 1 only: set up, warm up, time
+the K steps, print the JSON line.  ``--full`` adds phases 2-4 (a few minutes on 1 GPU).
+``--dump-outputs DIR`` writes what the last timed step left with the caller (parameters, gradients,
+optimizer and BatchNorm state, the window's loss / accuracy counters) as ``DIR/<name>.npy``; the inputs
+depend only on the arguments, so two builds can be compared array for array.
 """
 from __future__ import annotations
 
@@ -79,7 +83,40 @@ def parse():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--dtype', default=os.environ.get('RAFIKI_DTYPE', 'fp32'), choices=('fp32', 'bf16'),
                     help='compute dtype (fp32 = the reference precision; bf16 is opt-in)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run phases 2-4 (HPO trials, overhead probe, ensemble serving, the other BASELINE '
+                         'configs); without it only the phase 1 headline is measured')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the arrays the last step produced as DIR/<name>.npy')
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # all dumped arrays together (float32 / float64) stay below this
+DUMP_SAMPLE_SEED = 1234
+
+
+def dump_outputs(out_dir, arrays):
+    """Write ``arrays`` (name -> tensor) as ``out_dir/<name>.npy`` in float32 (float64 stays float64).  When
+    they exceed the byte budget together, every array larger than an equal share is reduced to a fixed,
+    seeded sample of its flattened elements (the same indices in every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        host[name] = t.cpu().numpy()
+    if sum(a.nbytes for a in host.values()) > DUMP_BUDGET_BYTES:
+        share = DUMP_BUDGET_BYTES // len(host)
+        for name in sorted(host):
+            a = host[name]
+            if a.nbytes > share:
+                rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+                keep = np.sort(rng.choice(a.size, size=share // a.itemsize, replace=False))
+                host[name] = a.reshape(-1)[keep]
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a))
+    return sorted(host)
 
 
 def phase_throughput(args, info, dev):
@@ -157,6 +194,13 @@ def phase_throughput(args, info, dev):
             advisor.feedback(proposals[r], float(table[r, 1]))
     out = dict(elapsed=elapsed, own_elapsed=own, loss=loss, acc=acc, knobs=proposals[0], dtype=eng.dtype,
                train_flops_per_image=eng.train_flops_per_image(), use_graph=use_graph)
+    if args.dump_outputs and info.is_main:
+        # what the training step hands back: the state after the last timed step and the window's counters
+        arrays = {'params': eng.flat.master, 'grads': eng.flat.grad, 'bn_running': eng.running,
+                  'loss_sum': eng.loss_sum, 'correct': eng.correct, 'seen': eng.seen}
+        for k, t in enumerate(eng._opt_tensors()):
+            arrays['opt_state{}'.format(k)] = t
+        out['dumped'] = dump_outputs(args.dump_outputs, arrays)
     del eng, data, y_all
     torch.cuda.empty_cache()
     return out
@@ -423,10 +467,10 @@ def main():
     serving = None
     tag = os.environ.get('MASTER_PORT', '0') if world > 1 else str(os.getpid())
     root = os.path.join(tempfile.gettempdir(), 'rafiki_bench_{}'.format(tag))
-    if args.trials > 0:
+    if args.full and args.trials > 0:
         _progress(info, 'phase 2: VggSmallTrial trials')
         trials = phase_trials(args, info, root, 'VggSmallTrial', args.trials, TRAIN_URI, TEST_URI)
-    if args.probe_trials > 0:
+    if args.full and args.probe_trials > 0:
         _progress(info, 'phase 2b: overhead-probe trials')
         probe = phase_trials(args, info, root, 'VggSmallProbe', args.probe_trials, PROBE_TRAIN_URI, PROBE_TEST_URI,
                              warm=False)
@@ -435,7 +479,7 @@ def main():
         _progress(info, 'phase 3: ensemble serving (device, then HTTP)')
         serving = phase_serving(src['db'], src['sub'], dev)
 
-    which = _configs(args, world)
+    which = _configs(args, world) if args.full else []
     cfgs = {}
     # ranks sharing a GPU (gloo rehearsal) skip it unless RAFIKI_BENCH_PGGAN_REHEARSAL=1 (the spawn / store path)
     if 'pggan' in which and (n_devices == world or os.environ.get('RAFIKI_BENCH_PGGAN_REHEARSAL') == '1'):
@@ -480,7 +524,10 @@ def main():
             'train_loss': round(th['loss'], 4),
             'train_acc': round(th['acc'], 4),
             'knobs_rank0': th['knobs'],
+            'full': args.full,
         }
+        if 'dumped' in th:
+            out['dumped_outputs'] = {'dir': args.dump_outputs, 'arrays': th['dumped']}
         if trials is not None:
             out['trials_per_hour_measured'] = round(trials['n'] * 3600.0 / trials['wall'], 1)
             out['trials_measured'] = trials['n']

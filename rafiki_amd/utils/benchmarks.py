@@ -1,5 +1,5 @@
-"""Measurement phases for the BASELINE.json configs other than the VGG-small headline (bench.py runs them
-after its own phases; scripts/bench_configs.py and scripts/bench_pg_gan.py run them stand-alone).
+"""Measurement phases for the BASELINE.json configs other than the VGG-small headline (bench.py --full runs
+them after its own phases; scripts/bench_configs.py and scripts/bench_pg_gan.py run them stand-alone).
 
   #1 ``skdt_trials``      SkDt single-trial random-search advisor on CPU: trials/hour through
                           propose -> train -> evaluate -> dump_parameters -> feedback

@@ -8,7 +8,7 @@
      synthetic CIFAR-shaped images, batch 256, width 1.0) -> evaluate (10k) -> dump_parameters ->
      feedback, timed per trial (measured trials/hour; bench.py reports the steady-state step rate)
 
-bench.py measures #1-#5 itself (#1, #2, #5 through rafiki_amd/utils/benchmarks.py); this script runs them
+bench.py --full measures #1-#5 itself (#1, #2, #5 through rafiki_amd/utils/benchmarks.py); this script runs them
 stand-alone.
 """
 import argparse

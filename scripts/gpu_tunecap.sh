@@ -12,7 +12,7 @@ OUT=gpurun_out/tunecap
 mkdir -p $OUT /tmp/shipped_seed
 mv rafiki_amd/tune/*.json /tmp/shipped_seed/
 export RAFIKI_TUNE_CACHE=$PWD/$OUT/fresh.json
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $OUT/bench_fresh.json 2> $OUT/bench_fresh.err
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_fresh.json 2> $OUT/bench_fresh.err
 for mb in 256 128 64; do
   timeout -k 10 300 python scripts/bench_pg_gan.py --lods 3 --minibatch $mb --steps 3 --warmup 3 >> $OUT/pg_dp_shapes.jsonl 2>/dev/null
 done
