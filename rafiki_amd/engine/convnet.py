@@ -412,10 +412,7 @@ class ConvNetEngine:
         acts, saved, h = [x], [], x
         pros, hpro = [None], None   # normalise-on-load: the BN coeffs acts[bi] still needs applied (or None)
         for bi, (name, cin, cout, pool, hw) in enumerate(self.blocks):
-            wk = dict(wino=ww.lazy('u2', bi) if ww is not None else None,
-                      wino4=ww.lazy('u4', bi) if ww is not None else None,
-                      wino4p=ww.lazy('u4p', bi) if ww is not None else None,
-                      wino4b=ww.lazy('u4b', bi) if ww is not None else None)
+            wk = ww.conv_sets(bi) if ww is not None else {}
             if not self.bn:
                 # conv + bias (+ ReLU in the epilogue when no pool follows; the saved post-ReLU output
                 # gives the same mask); a pooled block runs ReLU + max-pool in the eval-BN kernel
@@ -517,12 +514,8 @@ class ConvNetEngine:
                 break
             py, pco = saved[bi - 1]
             pname, pcin, pcout, ppool, phw = self.blocks[bi - 1]
-            wu = ww.lazy('ut2', bi) if ww is not None else None
-            wu4 = ww.lazy('ut4', bi) if ww is not None else None
-            wu4p = ww.lazy('ut4p', bi) if ww is not None else None
-            wu4b = ww.lazy('ut4b', bi) if ww is not None else None
             wl = wt.lazy(bi - 1)
-            dk = dict(wino=wu, wino4=wu4, cin=cin, wino4p=wu4p, wino4b=wu4b)
+            dk = dict(ww.conv_sets(bi, dgrad=True) if ww is not None else {}, cin=cin)
             if not ppool:
                 # the input block is BN+ReLU: its mask and BN-backward sums ride in this dgrad's epilogue
                 d = S.conv_dgrad(dy, wl, bnb=(py, pco, accs[bi - 1][1]), **dk)

@@ -71,13 +71,11 @@ _SIGS = {
     "rk_lstm_fwd32": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "rk_lstm_bwd32": [vp, i32, i32, i32, vp, vp, vp, vp, vp],
     "rk_wino_weights": [vp, vp, vp, i32, i32, vp],
-    "rk_wino_weights_multi": [vp, vp, vp, i32, vp, vp],
     "rk_wino_conv_grp": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, vp],
     "rk_wino_wgrad": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "rk_wino_conv": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "rk_wino4_weights": [vp, vp, vp, i32, i32, vp],
     "rk_wino4b_weights": [vp, vp, vp, i32, i32, vp],
-    "rk_wino4_weights_multi": [vp, vp, vp, i32, vp, vp],
     "rk_wino4_conv_grp": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, vp],
     "rk_wino4_conv": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "rk_wino4_conv_pro": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp],
@@ -85,7 +83,6 @@ _SIGS = {
     "rk_wino4_pt_transform_pro": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp],
     "rk_wino4_pt_input_pro": [vp, vp, i32, i32, i32, i32, vp, vp],
     "rk_x6p_w4_input_pro": [vp, vp, i32, i32, i32, i32, vp, vp],
-    "rk_wino4_wgrad": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "rk_wino4_wgrad_v": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "rk_wino4_pt_transform": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "rk_wino4_pt_output": [vp, vp, i32, i32, i32, i32, i64, vp],
@@ -139,7 +136,6 @@ _SIGS = {
     "rk_x6p_split": [vp, vp, i32, i32, i32, i32, i64, vp],
     "rk_x6p_split_t": [vp, vp, i32, i32, i32, i32, i64, vp],
     "rk_x6p_w4_weights": [vp, vp, vp, i32, i32, vp],
-    "rk_x6p_w4_weights_multi": [vp, vp, vp, i32, vp, vp],
     "rk_wino_weights_all": [vp, vp, vp, i32, vp, vp],
     "rk_x6p_w4_input": [vp, vp, i32, i32, i32, i32, vp],
     "rk_x6p_w4_wgrad_transform": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],

@@ -192,6 +192,19 @@ def _wt(kind, w, fn):
     return get
 
 
+# producers of the Winograd-domain sets of one conv weight, by WinoWeights kind (no blocked sets here)
+_WINO_SETS = {'u2': S.wino_u, 'ut2': S.wino_ut, 'u4': S.wino4_u, 'ut4': S.wino4_ut, 'u4p': S.wino4_u4p,
+              'ut4p': lambda wd: S.wino4_u4p(wd, dgrad=True)}
+
+
+def _wino_sets(w, wd, taps, dgrad=False):
+    """The weight-set kwargs of S.conv_fwd / S.conv_dgrad for weight ``w`` (``wd``: detached, contiguous):
+    each set a callable, cached per weight inside ``cached_weight_transforms``."""
+    if taps != 9:
+        return {}
+    return S.conv_sets(lambda kind: _wt(kind, w, lambda: _WINO_SETS[kind](wd)) if kind in _WINO_SETS else None, dgrad)
+
+
 # Observer of in-place gradient writes: GRAD_WATCH[0](leaf) is called right before a backward enqueues a
 # contribution into a leaf's persistent .grad buffer (parallel/grad_bucket.py places each bucket's
 # all-reduce event after the bucket's last contribution).  Process-global: the backward of a CUDA graph
@@ -279,9 +292,7 @@ class ConvFn(torch.autograd.Function):
             wd = w.detach().contiguous()
             # 3x3: the fused Winograd kernels (weights transformed inside the candidate) compete in the tuner
             y = S.conv_fwd(x, wd, taps=taps, bias=bd, act=_act(slope), slope=0.2 if slope is None else slope,
-                           wino=_wt('u2', w, lambda: S.wino_u(wd)) if taps == 9 else None,
-                           wino4=_wt('u4', w, lambda: S.wino4_u(wd)) if taps == 9 else None,
-                           wino4p=_wt('u4p', w, lambda: S.wino4_u4p(wd)) if taps == 9 else None)
+                           **_wino_sets(w, wd, taps))
         else:
             y = F.conv_fwd(x, _wshadow(w, wb), taps=taps, bias=bd, act=_act(slope),
                            slope=0.2 if slope is None else slope)
@@ -332,10 +343,7 @@ class ConvDgradFn(torch.autograd.Function):
         if gy.dtype == F32:
             wd = w.detach().contiguous()
             dx = S.conv_dgrad(gy, _wt('wt%d' % taps, w, lambda: S.conv_wt(wd, taps)), taps=taps,
-                              cin=wd.numel() // (taps * wd.shape[0]),
-                              wino=_wt('ut2', w, lambda: S.wino_ut(wd)) if taps == 9 else None,
-                              wino4=_wt('ut4', w, lambda: S.wino4_ut(wd)) if taps == 9 else None,
-                              wino4p=_wt('ut4p', w, lambda: S.wino4_u4p(wd, dgrad=True)) if taps == 9 else None)
+                              cin=wd.numel() // (taps * wd.shape[0]), **_wino_sets(w, wd, taps, dgrad=True))
         else:
             dx = F.conv_dgrad(gy, _wshadow(w, wb), taps=taps)
         ctx.save_for_backward(gy, w)

@@ -15,7 +15,8 @@ picked per layer shape by the autotuner (``rafiki_amd.ops.autotune``) outside ca
 from __future__ import annotations
 
 import os
-from typing import Optional
+from functools import partial
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -41,8 +42,6 @@ USE_X6 = os.environ.get('RAFIKI_X6', '1') != '0'
 def tile_dims(t: int):
     """(BM, BN) of a tile code (X6 codes included)."""
     return TILES[t & 15]
-
-
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -128,7 +127,7 @@ def _cands(M, N, splittable=False, K=0, big=False):
                     if c not in out:
                         out.append(c)
     if USE_X6:
-        x6 = [(t + X6, nst, s) for (t, nst, s) in out if t < 4 or t >= 4]
+        x6 = [(t + X6, nst, s) for (t, nst, s) in out]
         # the few-wave 64x64-wave-tile shapes, X6 only (their point is the split VALU per MFMA)
         for t in _FEW_WAVE:
             bm, bn = TILES[t]
@@ -158,6 +157,39 @@ def _slots_flags(acc):
 
 
 # ------------------------------------------------------------------------------------------ conv
+# cfg[0] >= 0 is the direct implicit-GEMM kernel, cfg = (tile code, ring depth, K splits); cfg[0] < 0 names a
+# route of CONV_ROUTES / WGRAD_ROUTES (the route table below), which also says what cfg[1:] hold.
+SET_KWARGS = ('wino', 'wino4', 'wino4p', 'wino4b')   # the weight-set kwargs of conv_fwd / conv_dgrad
+_SET_KINDS = (('u2', 'u4', 'u4p', 'u4b'), ('ut2', 'ut4', 'ut4p', 'ut4b'))   # their WinoWeights kinds (fwd, dgrad)
+
+
+def conv_sets(lazy, dgrad=False):
+    """The weight-set kwargs of conv_fwd (``dgrad``: conv_dgrad) from ``lazy(kind)``: a callable producing
+    the WinoWeights-kind set, or None where the layer has none."""
+    return {kw: lazy(kind) for kw, kind in zip(SET_KWARGS, _SET_KINDS[bool(dgrad)])}
+
+
+def _offered(families, sets, taps, H, W, C, N, need):
+    """(per route family: is it offered to this conv of C input / N output channels?, the candidates of those
+    that are).  ``need``: the E_* options the call takes.  Computed once per call: the flags also go into its key."""
+    on = [sets[f.weights] is not None and taps == 9 and not (need & ~f.also) and f.offer(H, W, C, N)
+          for f in families]
+    return on, [c for f, o in zip(families, on) if o for c in f.cfgs]
+
+
+def _sets_key(sets, on):
+    """The weight-set slots of a conv tune key: 'lazy' where the set is produced on demand (the candidate
+    then times transform + conv), else whether its family is offered."""
+    w2, w4, w4b, pt, ptx = on
+    return (('lazy' if callable(sets[0]) else w2, 'lazy' if callable(sets[1]) else w4, pt,
+             'lazy' if callable(sets[2]) else ptx) + (('b', 'lazy' if callable(sets[3]) else True),) * w4b)
+
+
+def _run_route(r, x, sets, out, cfg, epi):
+    u = sets[r.weights]
+    r.kernel(x, u() if callable(u) else u, out=out, **SLOTS[r.slots](r, cfg), **epi)
+
+
 def conv_fwd(x: torch.Tensor, w: torch.Tensor, *, taps: int = 9, stats_acc=None, bias=None, act=ACT_NONE,
              slope=0.2, out=None, wino=None, wino4=None, wino4p=None, wino4b=None, pro=None):
     """y = conv3x3(x, w) (stride 1, pad 1; taps=1: 1x1) [+bias][act]; with ``stats_acc`` (zeroed fp64
@@ -165,7 +197,8 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, *, taps: int = 9, stats_acc=None,
     ``wino``: the layer's Winograd weights (WinoWeights.u), or a callable producing them (run only
     when a Winograd candidate runs, so the tuner times transform + conv) -> the fused F(2x2,3x3)
     kernels are more autotune candidates; ``wino4`` likewise for the F(4x4,3x3) kernels (WinoWeights.u4),
-    ``wino4p`` the X6 weight planes (WinoWeights 'u4p') of the pre-split pre-transformed F(4x4) path.
+    ``wino4p`` the X6 weight planes (WinoWeights 'u4p') of the pre-split pre-transformed F(4x4) path,
+    ``wino4b`` the blocked F(4x4) set ('u4b').
     ``pro``: normalise-on-load — x is the pre-BN output y of the previous conv, pro = its coeffs
     (bn_finalize): every candidate loads relu(y * scale + shift) (the F(4x4) kernels with blocked weights
     and the pre-transformed paths; see bn_on_load_ok)."""
@@ -178,38 +211,27 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, *, taps: int = 9, stats_acc=None,
         out = torch.empty((Nb, H, W, Cout), device=x.device, dtype=torch.float32)
     flags = (F_STATS if stats_acc is not None else 0) | (F_BIAS if bias is not None else 0)
     flags |= F_RELU if act == ACT_RELU else F_LRELU if act == ACT_LRELU else 0
-
-    use_w = wino is not None and taps == 9 and wino_ok(H, W, Cin) and act in (ACT_NONE, ACT_RELU)
-    use_w4 = wino4 is not None and taps == 9 and wino4_ok(H, W, Cin) and act in (ACT_NONE, ACT_RELU)
-    use_w4b = wino4b is not None and taps == 9 and wino4_ok(H, W, Cin) and act in (ACT_NONE, ACT_RELU)
-    # the pre-transformed paths also carry a leaky-ReLU epilogue (no statistics with it): PG-GAN's D convs
-    act_pt = act in (ACT_NONE, ACT_RELU) or (act == ACT_LRELU and stats_acc is None)
-    use_pt = (wino4 is not None and taps == 9 and wino4_ok(H, W, Cin) and act_pt and wino4_pt_ok(H, W, Cin, Cout))
-    use_ptx = wino4p is not None and taps == 9 and wino4_ptx_ok(H, W, Cin, Cout) and act_pt
-    lrelu = slope if act == ACT_LRELU else None
+    sets = (wino, wino4, wino4p, wino4b)
+    epi = dict(bias=bias, stats=stats_acc, relu=act == ACT_RELU)
+    need = 0
+    if act == ACT_LRELU:   # rides (without statistics) only in the pre-transformed paths' epilogue: PG-GAN's D convs
+        need, epi['lrelu'] = E_LRELU if stats_acc is None else E_DIRECT, slope
+    if pro is not None:   # only the kernels that normalise on load are candidates
+        assert bias is None and act == ACT_NONE and pro.shape == (4, Cin)
+        need, epi['pro'], cands = E_PRO, pro, []
+    else:
+        cands = _cands(M, Cout, splittable=stats_acc is None and Cout % 4 == 0, K=K, big=Cin % 32 == 0)
+    on, fused = _offered(CONV_FAMILIES, sets, taps, H, W, Cin, Cout, need)
+    cands += fused
+    if not cands:
+        raise ValueError('conv_fwd(pro=...): no normalise-on-load kernel for this shape (see bn_on_load_ok)')
 
     def run(cfg):
+        r = CONV_ROUTES.get(cfg[0])
+        if r is not None:
+            _run_route(r, x, sets, out, cfg, epi)
+            return
         tile, nst, s = cfg
-        if tile == WINO4_PTX:
-            wino4_conv_pt(x, wino4p() if callable(wino4p) else wino4p, out=out, bias=bias, stats=stats_acc,
-                          relu=act == ACT_RELU, tile=nst // 4, nst=nst % 4, splits=s, lrelu=lrelu, pro=pro)
-            return
-        if tile == WINO4_PT:
-            wino4_conv_pt(x, wino4() if callable(wino4) else wino4, out=out, bias=bias, stats=stats_acc,
-                          relu=act == ACT_RELU, tile=nst, nst=s, lrelu=lrelu, pro=pro)
-            return
-        if cfg in WINO4_CFGS:
-            wino4_conv(x, wino4() if callable(wino4) else wino4, out=out, bias=bias, stats=stats_acc,
-                       relu=act == ACT_RELU, variant=_wino4_variant(cfg))
-            return
-        if cfg in WINO4B_CFGS:
-            wino4_conv(x, wino4b() if callable(wino4b) else wino4b, out=out, bias=bias, stats=stats_acc,
-                       relu=act == ACT_RELU, variant=_WINO4B_VARIANT[cfg[0]], n_out=Cout, pro=pro)
-            return
-        if cfg in WINO_CFGS:
-            wino_conv(x, wino() if callable(wino) else wino, out=out, bias=bias, stats=stats_acc,
-                      relu=act == ACT_RELU, variant=_wino_variant(cfg))
-            return
         if s == 1:
             sgemm(KIND_CONV, x, w, out, M, Cout, K, Cin, K, Cout, tile=tile, nst=nst, bias=bias, stats=stats_acc,
                   H=H, W=W, C=Cin, taps=taps, flags=flags, slope=slope)
@@ -220,28 +242,8 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, *, taps: int = 9, stats_acc=None,
         sgemm(KIND_CONV, x, w, slab, M, Cout, K, Cin, K, Cout, tile=tile, nst=nst, splits=s, slab_stride=M * Cout,
               H=H, W=W, C=Cin, taps=taps)
         sreduce_epi(slab, M, Cout, out.view(M, Cout), bias=bias, act=act, slope=slope)
-    if pro is not None:   # only the kernels that normalise on load are candidates
-        assert bias is None and act == ACT_NONE and pro.shape == (4, Cin)
-        use_w = use_w4 = False
-        cands = []
-    else:
-        cands = _cands(M, Cout, splittable=stats_acc is None and Cout % 4 == 0, K=K, big=Cin % 32 == 0)
-    if use_w:
-        cands.extend(WINO_CFGS)
-    if use_w4:
-        cands.extend(WINO4_CFGS)
-    if use_w4b:
-        cands.extend(WINO4B_CFGS)
-    if use_pt:
-        cands.extend(WINO4_PT_CFGS)
-    if use_ptx:
-        cands.extend(WINO4_PTX_CFGS)
-    if not cands:
-        raise ValueError('conv_fwd(pro=...): no normalise-on-load kernel for this shape (see bn_on_load_ok)')
-    cfg = _pick(('sf', M, Cout, K, H, W, Cin, taps, flags, 'lazy' if callable(wino) else use_w,
-                 'lazy' if callable(wino4) else use_w4, use_pt, 'lazy' if callable(wino4p) else use_ptx)
-                + (('b', 'lazy' if callable(wino4b) else True),) * use_w4b + (('pro',) if pro is not None else ()),
-                cands, run)
+    cfg = _pick(('sf', M, Cout, K, H, W, Cin, taps, flags) + _sets_key(sets, on)
+                + (('pro',) if pro is not None else ()), cands, run)
     if stats_acc is not None and autotune.can_tune():
         stats_acc.zero_()  # tuning runs accumulated into it
     run(cfg)
@@ -250,13 +252,15 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, *, taps: int = 9, stats_acc=None,
 
 def conv_dgrad(dy: torch.Tensor, wt, *, taps: int = 9, out=None, gate=None, bnb=None, bnp=None,
                wino=None, wino4=None, cin=None, wino4p=None, wino4b=None):
-    """dx = data gradient of a 3x3 conv as conv3x3(dy, wt) with wt = SConvWT.view() [Cin][taps*Cout].
+    """dx = data gradient of a 3x3 conv as conv3x3(dy, wt) with wt = SConvWT.view() [Cin][taps*Cout]: the
+    same routes as conv_fwd on the data-gradient sets (``wino``: WinoWeights.ut, ``wino4`` 'ut4', ``wino4p``
+    'ut4p', ``wino4b`` 'ut4b').
     Epilogue options: ``gate`` (ReLU mask of the input activation), ``bnb = (y, coeffs, acc)`` (the input
     is BN+ReLU(y): mask + BN-backward sums into acc), ``bnp = (y, coeffs, acc)`` (the input is
     maxpool(BN+ReLU(y)), y at 2x resolution: routing + sums; dx stays the pooled gradient)."""
     _check(dy, 'conv_dgrad dy')
     Nb, H, W, Cout = dy.shape
-    # wt / wino may be callables (weights prepared per call, inside the timed candidate): then ``cin``
+    # wt / the sets may be callables (weights prepared per call, inside the timed candidate): then ``cin``
     Cin = cin if callable(wt) else wt.shape[0]
     M, K = Nb * H * W, taps * Cout
     assert callable(wt) or wt.numel() == Cin * K
@@ -274,55 +278,32 @@ def conv_dgrad(dy: torch.Tensor, wt, *, taps: int = 9, out=None, gate=None, bnb=
         gate, bias, flags = y, coeffs[2:4].reshape(-1), F_BNP
     elif gate is not None:
         flags = F_GATE
-    # ``wino``: the layer's Winograd data-gradient weights (WinoWeights.ut), one more candidate
-    use_w = wino is not None and taps == 9 and wino_ok(H, W, Cout) and not (flags & F_GATE)
-    use_w4 = wino4 is not None and taps == 9 and wino4_ok(H, W, Cout) and not (flags & F_GATE)
-    use_w4b = wino4b is not None and taps == 9 and wino4_ok(H, W, Cout) and not (flags & F_GATE)
-
-    use_pt = use_w4 and wino4_pt_ok(H, W, Cout, Cin)
-    # ``wino4p``: the X6 planes of the data-gradient set (WinoWeights 'ut4p'): the pre-split PT path
-    use_ptx = wino4p is not None and taps == 9 and wino4_ptx_ok(H, W, Cout, Cin) and not (flags & F_GATE)
+    sets = (wino, wino4, wino4p, wino4b)
+    epi = dict(bnb=bnb, bnp=bnp)
+    on, fused = _offered(CONV_FAMILIES, sets, taps, H, W, Cout, Cin, E_DIRECT if flags & F_GATE else 0)
+    cands = _cands(M, Cin, big=Cout % 32 == 0) + fused
 
     def run(cfg):
-        if cfg[0] == WINO4_PTX:
-            wino4_conv_pt(dy, wino4p() if callable(wino4p) else wino4p, out=out, bnb=bnb, bnp=bnp, tile=cfg[1] // 4,
-                          nst=cfg[1] % 4, splits=cfg[2])
+        r = CONV_ROUTES.get(cfg[0])
+        if r is not None:
+            _run_route(r, dy, sets, out, cfg, epi)
             return
-        if cfg[0] == WINO4_PT:
-            wino4_conv_pt(dy, wino4() if callable(wino4) else wino4, out=out, bnb=bnb, bnp=bnp, tile=cfg[1],
-                          nst=cfg[2])
-            return
-        if cfg in WINO4_CFGS:
-            wino4_conv(dy, wino4() if callable(wino4) else wino4, out=out, bnb=bnb, bnp=bnp,
-                       variant=_wino4_variant(cfg))
-            return
-        if cfg in WINO4B_CFGS:
-            wino4_conv(dy, wino4b() if callable(wino4b) else wino4b, out=out, bnb=bnb, bnp=bnp,
-                       variant=_WINO4B_VARIANT[cfg[0]], n_out=Cin)
-            return
-        if cfg in WINO_CFGS:
-            wino_conv(dy, wino() if callable(wino) else wino, out=out, bnb=bnb, bnp=bnp, variant=_wino_variant(cfg))
-            return
-        sgemm(KIND_CONV, dy, wt() if callable(wt) else wt, out, M, Cin, K, Cout, K, Cin, tile=cfg[0], nst=cfg[1], bias=bias, stats=stats,
-              gate=gate, H=H, W=W, C=Cout, taps=taps, flags=flags)
-    cands = _cands(M, Cin, big=Cout % 32 == 0)
-    if use_w:
-        cands.extend(WINO_CFGS)
-    if use_w4:
-        cands.extend(WINO4_CFGS)
-    if use_w4b:
-        cands.extend(WINO4B_CFGS)
-    if use_pt:
-        cands.extend(WINO4_PT_CFGS)
-    if use_ptx:
-        cands.extend(WINO4_PTX_CFGS)
-    cfg = _pick(('sd', M, Cin, K, H, W, Cout, taps, flags, 'lazy' if callable(wino) else use_w,
-                 'lazy' if callable(wino4) else use_w4, use_pt, 'lazy' if callable(wino4p) else use_ptx)
-                + (('b', 'lazy' if callable(wino4b) else True),) * use_w4b, cands, run)
+        sgemm(KIND_CONV, dy, wt() if callable(wt) else wt, out, M, Cin, K, Cout, K, Cin, tile=cfg[0], nst=cfg[1],
+              bias=bias, stats=stats, gate=gate, H=H, W=W, C=Cout, taps=taps, flags=flags)
+    cfg = _pick(('sd', M, Cin, K, H, W, Cout, taps, flags) + _sets_key(sets, on), cands, run)
     if stats is not None and autotune.can_tune():
         stats.zero_()
     run(cfg)
     return out
+
+
+def _lead_with_split(cands, M, N):
+    """The split-K configs fill the chip: lead with the best-filling heuristic one."""
+    split = [c for c in cands if c[2] > 1]
+    if not split:
+        return cands
+    return [max(split, key=lambda c: min(cdiv(M, tile_dims(c[0])[0]) * cdiv(N, tile_dims(c[0])[1]) * c[2],
+                                         2 * NUM_CU))] + cands
 
 
 def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, *, taps: int = 9, out=None, accumulate=False, xpro=None):
@@ -336,21 +317,25 @@ def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, *, taps: int = 9, out=None, ac
     M, N, K = Cout, taps * Cin, Nb * H * W
     if out is None:
         out = torch.empty((Cout, N), device=dy.device, dtype=torch.float32)
+    pro = {}
+    if xpro is not None:
+        assert taps == 9 and xpro.shape == (4, Cin)
+        pro['xpro'] = xpro
+    # per route its candidates for this problem ([]: not offered): they feed the candidate list and the key
+    found = [r.offer(Nb, H, W, Cout, Cin) if taps == 9 and (xpro is None or r.also & E_PRO) else []
+             for r in WGRAD_ROUTES.values()]
+    cands = [] if pro else _lead_with_split(_cands(M, N, splittable=True, K=K, big=True), M, N)
+    for f in found:
+        cands = cands + f
+    if not cands:
+        raise ValueError('conv_wgrad(xpro=...): no normalise-on-load kernel for this shape (see bn_on_load_ok)')
 
     def run(cfg):
+        r = WGRAD_ROUTES.get(cfg[0])
+        if r is not None:
+            r.kernel(dy, x, out, accumulate=accumulate, **SLOTS[r.slots](r, cfg), **pro)
+            return
         tile, nst, s = cfg
-        if tile == WINO_WGRAD:
-            wino_wgrad(dy, x, out, splits=s, accumulate=accumulate)
-            return
-        if tile == WINO4_WGRAD:
-            wino4_wgrad(dy, x, out, splits=s, accumulate=accumulate, variant=nst, xpro=xpro)
-            return
-        if tile == WINO4_WGRAD_PT:
-            wino4_wgrad_pt(dy, x, out, accumulate=accumulate, tile=nst, nst=s, xpro=xpro)
-            return
-        if tile == WINO4_WGRAD_PTX:
-            wino4_wgrad_pt(dy, x, out, accumulate=accumulate, tile=nst // 4, nst=nst % 4, planes=True, splits=s)
-            return
         if s == 1:
             sgemm(KIND_WGRAD, dy, x, out, M, N, K, Cout, Cin, N, tile=tile, nst=nst, H=H, W=W, C=Cin, taps=taps,
                   flags=F_ACCUM if accumulate else 0)
@@ -359,26 +344,8 @@ def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, *, taps: int = 9, out=None, ac
         sgemm(KIND_WGRAD, dy, x, slab, M, N, K, Cout, Cin, N, tile=tile, nst=nst, splits=s, slab_stride=M * N,
               H=H, W=W, C=Cin, taps=taps)
         reduce_slabs(slab, out, accumulate=accumulate)
-    cands = _cands(M, N, splittable=True, K=K, big=True)
-    # the split-K configs fill the chip: lead with the best-filling heuristic one
-    split = [c for c in cands if c[2] > 1]
-    if split:
-        cands = [max(split, key=lambda c: min(cdiv(M, tile_dims(c[0])[0]) * cdiv(N, tile_dims(c[0])[1]) * c[2],
-                                              2 * NUM_CU))] + cands
-    wcands = _wino_wgrad_cands(Nb, H, W, Cout, Cin) if taps == 9 else []
-    w4cands = _wino4_wgrad_cands(Nb, H, W, Cout, Cin) if taps == 9 else []
-    ptcands = _wino4_pt_cands(Nb, H, W, Cout, Cin) if taps == 9 else []
-    ptxcands = _wino4_ptx_wgrad_cands(Nb, H, W, Cout, Cin) if taps == 9 else []
-    if xpro is not None:
-        assert taps == 9 and xpro.shape == (4, Cin)
-        cands, wcands, ptxcands = w4cands + ptcands, [], []
-        if not cands:
-            raise ValueError('conv_wgrad(xpro=...): no normalise-on-load kernel for this shape (see bn_on_load_ok)')
-    else:
-        cands += wcands + w4cands + ptcands + ptxcands
-    cfg = _pick(('sw', M, N, K, H, W, Cin, taps, bool(accumulate), bool(wcands), bool(w4cands), bool(ptcands),
-                 bool(ptxcands)) + (('pro',) if xpro is not None else ()), cands, run,
-                protect=(out,) if accumulate else ())
+    cfg = _pick(('sw', M, N, K, H, W, Cin, taps, bool(accumulate)) + tuple(bool(f) for f in found)
+                + (('pro',) if pro else ()), cands, run, protect=(out,) if accumulate else ())
     run(cfg)
     return out
 
@@ -435,19 +402,6 @@ class SConvWT:
 # -------------------------------------------------------------------- Winograd F(2x2, 3x3) convs
 WF_RELU, WF_BIAS, WF_STATS, WF_LRELU, WF_BNB, WF_BNP, WF_POOL = 1, 2, 4, 8, 512, 1024, 2048
 WINO = os.environ.get('RAFIKI_WINOGRAD', '1') != '0'
-# autotune candidates that run rk_wino_conv: 4-wave 64x32 tiles (variant 0) / 8-wave 64x64 (variant 1),
-# and the 16x16-wave-tile kernels of winograd4.hip: 4-wave 32x32 (variant 2), 2-wave 16x32 (variant 3),
-# 8-wave 64x32 (variant 4)
-# software-pipelined (two LDS stage) variants: the F(2x2) 8-wave one wins the 4x4-map layers and is a
-# candidate; the F(4x4) ones (one wave per SIMD) measured 1.3-1.5x slower than the single-stage kernels on
-# every VGG-small layer (profiles/winograd_variants_r2e.jsonl) and are not offered to the tuner (kept
-# callable as variant 2 of rk_wino4_conv / rk_wino4_wgrad_v, exercised by tests/test_winograd4_gpu.py)
-WINO_CFGS = ((-1, 0, 1), (-2, 0, 1), (-8, 0, 1), (-9, 0, 1), (-10, 0, 1), (-12, 0, 1))
-_WINO_VARIANT = {-1: 0, -2: 1, -8: 2, -9: 3, -10: 4, -12: 5}   # -12: 8-wave 64x32, two-stage pipelined
-
-
-def _wino_variant(cfg):
-    return _WINO_VARIANT[cfg[0]]
 
 
 def wino_ok(H: int, W: int, C: int) -> bool:
@@ -482,6 +436,25 @@ def wino_ut(w: torch.Tensor) -> torch.Tensor:
     return ut
 
 
+def _wino_epilogue(out, bias, stats, relu, bnb, bnp):
+    """(flags, bias, stats, gate) of a Winograd conv's epilogue: bias / ReLU / BN statistics, or with ``bnb``
+    / ``bnp`` = (y, coeffs, acc) the BN-backward forms of conv_dgrad (gate = y, bias = BN scale | shift)."""
+    Nb, H, W, N = out.shape
+    flags = (WF_BIAS if bias is not None else 0) | (WF_RELU if relu else 0) | (WF_STATS if stats is not None else 0)
+    gate = None
+    if bnb is not None:
+        gate, coeffs, stats = bnb
+        assert gate.shape == out.shape
+        bias, flags = coeffs[2:4].reshape(-1).contiguous(), WF_BNB
+    elif bnp is not None:
+        gate, coeffs, stats = bnp
+        assert gate.shape == (Nb, 2 * H, 2 * W, N)
+        bias, flags = coeffs[2:4].reshape(-1).contiguous(), WF_BNP
+    if stats is not None:
+        assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.shape[-1] == N
+    return flags, bias, stats, gate
+
+
 def wino_conv(x: torch.Tensor, u: torch.Tensor, *, out=None, bias=None, stats=None, relu=False, bnb=None, bnp=None,
               variant=0):
     """y = conv3x3(x, w) (stride 1, pad 1) from u = wino_weights(w): x [Nb, H, W, C] fp32 NHWC.
@@ -493,23 +466,7 @@ def wino_conv(x: torch.Tensor, u: torch.Tensor, *, out=None, bias=None, stats=No
     if out is None:
         out = torch.empty((Nb, H, W, N), device=x.device, dtype=torch.float32)
     assert out.shape == (Nb, H, W, N) and out.is_contiguous()
-    flags, gate = 0, None
-    if bias is not None:
-        flags |= WF_BIAS
-    if relu:
-        flags |= WF_RELU
-    if stats is not None:
-        flags |= WF_STATS
-    if bnb is not None:
-        gate, coeffs, stats = bnb
-        assert gate.shape == out.shape
-        bias, flags = coeffs[2:4].reshape(-1), WF_BNB
-    elif bnp is not None:
-        gate, coeffs, stats = bnp
-        assert gate.shape == (Nb, 2 * H, 2 * W, N)
-        bias, flags = coeffs[2:4].reshape(-1), WF_BNP
-    if stats is not None:
-        assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.shape[-1] == N
+    flags, bias, stats, gate = _wino_epilogue(out, bias, stats, relu, bnb, bnp)
     if variant >= 2:   # the small-wave-tile F(2x2) kernels (csrc/kernels/winograd4.hip): small grids
         _lib.call("rk_wino2s_conv_grp", _p(x), _p(u), _p(out), _p(bias), _p(stats), _slots_flags(stats), _p(gate),
                   Nb, H, W, C, N, flags, int(variant) - 2, 1, 0, 0, 0, 0, _s())
@@ -520,15 +477,7 @@ def wino_conv(x: torch.Tensor, u: torch.Tensor, *, out=None, bias=None, stats=No
 
 
 # ----------------------------------------------------------------- Winograd F(4x4, 3x3) forward
-# autotune candidates that run rk_wino4_conv: 8-wave 64 tiles x 32 channels (variant 0) / 4-wave 32 x 32
-# (variant 1) / 4-wave 32 x 32 over two LDS stages, software-pipelined (variant 2)
-WINO4_CFGS = ((-5, 0, 1), (-6, 0, 1))
-_WINO4_VARIANT = {-5: 0, -6: 1, -11: 2}
-
-
-def _wino4_variant(cfg):
-    return _WINO4_VARIANT[cfg[0]]
-WINO4 = os.environ.get('RAFIKI_WINOGRAD4', '1') != '0'
+WINO4 =os.environ.get('RAFIKI_WINOGRAD4', '1') != '0'
 
 
 def wino4_ok(H: int, W: int, C: int) -> bool:
@@ -567,14 +516,8 @@ def wino4_ut(w: torch.Tensor) -> torch.Tensor:
     return ut
 
 
-# blocked-weight variants of the fused F(4x4) kernel (weights as the kernel's LDS stage image, one contiguous
-# 36-KiB block per 32 output channels x 8 input channels: rk_wino4b_weights / WinoWeights 'u4b' / 'ut4b'):
-# variant 3 = variant 0's 8-wave tile, 4 = variant 1's 4-wave tile, 5 = warp-specialised (4 compute + 4 loader
-# waves over two LDS stages)
-WINO4B_CFGS = ((-17, 0, 1), (-18, 0, 1), (-19, 0, 1))
-_WINO4B_VARIANT = {-17: 3, -18: 4, -19: 5}
-
-
+# blocked F(4x4) sets: the weights as the fused kernel's LDS stage image, one contiguous 36-KiB block per 32
+# output channels x 8 input channels (rk_wino4b_weights / WinoWeights 'u4b' / 'ut4b'; variants 3-5 of wino4_conv)
 def wino4b_numel(N: int, C: int) -> int:
     """Floats of a blocked F(4x4) set with N output rows (padded to 32) and C input columns."""
     return 36 * cdiv(N, 32) * 32 * C
@@ -593,13 +536,13 @@ def wino4b_u(w: torch.Tensor, dgrad: bool = False) -> torch.Tensor:
 def wino4_conv(x: torch.Tensor, u: torch.Tensor, *, out=None, bias=None, stats=None, relu=False, bnb=None, bnp=None,
                variant=0, n_out=None, pro=None):
     """y = conv3x3(x, w) (stride 1, pad 1) by F(4x4,3x3) from u = wino4_u(w); options as wino_conv.
-    Variants 3 / 4 take the blocked set (wino4b_u / WinoWeights 'u4b'), flat, with ``n_out`` channels.
+    Variants 3-5 take the blocked set (wino4b_u / WinoWeights 'u4b'), flat, with ``n_out`` (default: out's) channels.
     ``pro``: normalise-on-load — x is the pre-BN output of the previous conv and pro its BN coeffs [4][C]
     (bn_finalize): the kernel loads relu(x * scale + shift) (blocked variants 3-5, no bias / activation)."""
     _check(x, 'wino4_conv x')
     Nb, H, W, C = x.shape
     if variant >= 3:
-        N = int(n_out)
+        N = int(out.shape[-1] if n_out is None else n_out)
         assert u.dim() == 1 and u.numel() == wino4b_numel(N, C) and u.is_contiguous(), (u.shape, N, C)
     else:
         N = u.shape[1]
@@ -607,23 +550,7 @@ def wino4_conv(x: torch.Tensor, u: torch.Tensor, *, out=None, bias=None, stats=N
     if out is None:
         out = torch.empty((Nb, H, W, N), device=x.device, dtype=torch.float32)
     assert out.shape == (Nb, H, W, N) and out.is_contiguous()
-    flags, gate = 0, None
-    if bias is not None:
-        flags |= WF_BIAS
-    if relu:
-        flags |= WF_RELU
-    if stats is not None:
-        flags |= WF_STATS
-    if bnb is not None:
-        gate, coeffs, stats = bnb
-        assert gate.shape == out.shape
-        bias, flags = coeffs[2:4].reshape(-1), WF_BNB
-    elif bnp is not None:
-        gate, coeffs, stats = bnp
-        assert gate.shape == (Nb, 2 * H, 2 * W, N)
-        bias, flags = coeffs[2:4].reshape(-1), WF_BNP
-    if stats is not None:
-        assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.shape[-1] == N
+    flags, bias, stats, gate = _wino_epilogue(out, bias, stats, relu, bnb, bnp)
     if pro is not None:
         assert variant >= 3 and flags in (0, WF_STATS) and pro.shape == (4, C) and pro.is_contiguous()
         _lib.call("rk_wino4_conv_pro", _p(x), _p(u), _p(out), None, _p(stats), _slots_flags(stats), None,
@@ -632,9 +559,6 @@ def wino4_conv(x: torch.Tensor, u: torch.Tensor, *, out=None, bias=None, stats=N
     _lib.call("rk_wino4_conv", _p(x), _p(u), _p(out), _p(bias), _p(stats), _slots_flags(stats), _p(gate),
               Nb, H, W, C, N, flags, int(variant), _s())
     return out
-
-
-WINO4_PT = -14   # pre-transformed F(4x4) conv: cfg = (-14, sgemm tile, sgemm nst)
 
 
 # largest map the pre-transformed paths are offered on: 8 with the f32 GEMM (they lost on 16x16 maps,
@@ -651,9 +575,12 @@ def wino4_pt_ok(H, W, C, N):
             and N >= 32)
 
 
-WINO4_PT_CFGS = tuple((WINO4_PT, t + x, n) for x in ((0, X6) if USE_X6 else (0,)) for t in (0, 1, 2, 3)
-                      for n in ((2, 3) if t in _NST3 else (2,))) + \
-    (tuple((WINO4_PT, t + X6, 2) for t in _FEW_WAVE) if USE_X6 else ())
+def _pt_cfgs(route_id):
+    """(id, sgemm tile, nst) of a pre-transformed path: the four-wave tiles x ring depths on the f32 and the X6
+    K loop, and the few-wave X6 tiles."""
+    return tuple((route_id, t + x, n) for x in ((0, X6) if USE_X6 else (0,)) for t in (0, 1, 2, 3)
+                 for n in ((2, 3) if t in _NST3 else (2,))) + \
+        (tuple((route_id, t + X6, 2) for t in _FEW_WAVE) if USE_X6 else ())
 
 
 def wino4_conv_pt(x: torch.Tensor, u: torch.Tensor, *, out=None, bias=None, stats=None, relu=False, bnb=None,
@@ -672,26 +599,10 @@ def wino4_conv_pt(x: torch.Tensor, u: torch.Tensor, *, out=None, bias=None, stat
     if out is None:
         out = torch.empty((Nb, H, W, N), device=x.device, dtype=torch.float32)
     assert out.shape == (Nb, H, W, N) and out.is_contiguous()
-    flags, gate = 0, None
-    if bias is not None:
-        flags |= WF_BIAS
-    if relu:
-        flags |= WF_RELU
+    flags, bias, stats, gate = _wino_epilogue(out, bias, stats, relu, bnb, bnp)
     if lrelu is not None:
-        assert not relu and stats is None and bnb is None and bnp is None
+        assert flags in (0, WF_BIAS)
         flags |= WF_LRELU
-    if stats is not None:
-        flags |= WF_STATS
-    if bnb is not None:
-        gate, coeffs, stats = bnb
-        assert gate.shape == out.shape
-        bias, flags = coeffs[2:4].reshape(-1).contiguous(), WF_BNB
-    elif bnp is not None:
-        gate, coeffs, stats = bnp
-        assert gate.shape == (Nb, 2 * H, 2 * W, N)
-        bias, flags = coeffs[2:4].reshape(-1).contiguous(), WF_BNP
-    if stats is not None:
-        assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.shape[-1] == N
     T = Nb * (H // 4) * (W // 4)
     if pro is not None:   # normalise-on-load in the input transform (pro = the producer's BN coeffs [4][C])
         assert pro.shape == (4, C) and pro.is_contiguous()
@@ -739,9 +650,6 @@ def wino4_conv_grp(x, u, *, out=None, bias=None, relu=False, variant=0, pool=Fal
               int(variant), G, 0 if shared else M * C, 36 * N * C, Nb * Ho * Wo * N, N if bias is not None else 0,
               _s())
     return out
-
-
-WINO4_WGRAD = -7  # autotune tile id of the F(4x4) weight gradient (cfg = (-7, 0, splits))
 
 
 def _wino4_wgrad_cands(Nb, H, W, Cout, Cin):
@@ -794,9 +702,6 @@ def wino4_wgrad(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor, *, splits=
     return out
 
 
-WINO4_WGRAD_PT = -13  # pre-transformed F(4x4) weight gradient: cfg = (-13, sgemm tile, sgemm nst)
-
-
 def _wino4_pt_cands(Nb, H, W, Cout, Cin):
     """The pre-transformed F(4x4) weight gradient (transform once, 36 GEMMs as one split-K sgemm) on
     maps of <= 8x8, where the fused kernels' redundant per-block transforms dominate (VGG-small batch
@@ -808,9 +713,7 @@ def _wino4_pt_cands(Nb, H, W, Cout, Cin):
     T = Nb * (H // 4) * (W // 4)
     if T % 32 or 36 * T * max(Cin, Cout) * 4 >= (1 << 31) or 36 * Cout * Cin * 4 > (512 << 20):
         return []
-    return [(WINO4_WGRAD_PT, t + x, n) for x in ((0, X6) if USE_X6 else (0,)) for t in (0, 1, 2, 3)
-            for n in ((2, 3) if t in _NST3 else (2,))] + \
-        ([(WINO4_WGRAD_PT, t + X6, 2) for t in _FEW_WAVE] if USE_X6 else [])
+    return list(_pt_cfgs(WINO4_WGRAD_PT))
 
 
 def wino4_wgrad_pt(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor, *, accumulate=False, tile=0, nst=2,
@@ -864,9 +767,15 @@ XP_NST3 = (0, 1, 2, 3, 4, 5, 6, 9, 10, 11, 12)   # tiles 7-8 (8 waves, 72 KiB pe
 # output transforms that read Y' / dU anyway)
 _XP_CFGS = tuple((t, n, 1) for t in range(len(XP_TILES)) for n in ((2, 3) if t in XP_NST3 else (2,))) + \
     tuple((t, 2, s) for t in (0, 1, 2, 7, 8) for s in (2, 4)) + tuple((t, 3, s) for t in (9, 10, 11) for s in (2, 4))
-WINO4_PTX = -15         # conv / data gradient: cfg = (-15, x6p code, splits), code = tile * 4 + nst
-WINO4_WGRAD_PTX = -16   # weight gradient: likewise
-WINO4_PTX_CFGS = tuple((WINO4_PTX, 4 * t + n, s) for t, n, s in _XP_CFGS) if USE_X6P else ()
+
+
+def x6p_pack(tile: int, nst: int) -> int:
+    """One config slot for an x6p GEMM's (tile, ring depth): the 'x6p code' of the PTX and dense routes."""
+    return 4 * tile + nst
+
+
+def x6p_unpack(code: int):
+    return code // 4, code % 4
 
 
 def x6p_split(src: torch.Tensor, out=None) -> torch.Tensor:
@@ -936,10 +845,7 @@ def _wino4_ptx_wgrad_cands(Nb, H, W, Cout, Cin):
     T = Nb * (H // 4) * (W // 4)
     if T % 32 or 108 * T * max(Cin, Cout) >= (1 << 31):
         return []
-    return [(WINO4_WGRAD_PTX, 4 * t + n, x6p_splits(T, s)) for t, n, s in _XP_CFGS]
-
-
-WINO_WGRAD = -3   # autotune tile id of the Winograd weight gradient (cfg = (-3, 0, splits))
+    return [(WINO4_WGRAD_PTX, x6p_pack(t, n), x6p_splits(T, s)) for t, n, s in _XP_CFGS]
 
 
 def _wino_wgrad_cands(Nb, H, W, Cout, Cin):
@@ -1003,6 +909,97 @@ def wino_conv_grp(x, u, *, out=None, bias=None, relu=False, variant=0, pool=Fals
     _lib.call(name, _p(x), _p(u), _p(out), _p(bias), None, 0, None, Nb, H, W, C, N, flags,
               v, G, 0 if shared else M * C, 16 * N * C, Nb * Ho * Wo * N, N if bias is not None else 0, _s())
     return out
+
+
+# ------------------------------------------------------------------------------- the route table
+# Every autotune candidate with cfg[0] < 0 is one row below; the dispatchers (conv_fwd, conv_dgrad, conv_wgrad,
+# conv_fwd_grp) look the row up by cfg[0] and call its kernel wrapper.  A data gradient is the same conv on the
+# transposed weight set with another epilogue, so forward and data gradient share the conv rows.
+class Route(NamedTuple):
+    id: int            # cfg[0]
+    name: str
+    slots: str         # what cfg[1], cfg[2] hold: a key of SLOTS, the decoder into the wrapper's kwargs
+    kernel: object     # the wrapper: conv kernel(x, u, out=, **slots, **epilogue); wgrad kernel(dy, x, out, ...)
+    offer: object      # conv: offer(H, W, C, N) -> the shape fits (C input, N output channels);
+    #                    weight gradient: offer(Nb, H, W, Cout, Cin) -> its candidates ([]: not offered)
+    cfgs: tuple = ()   # conv: its candidates, in the order the tuner sees them
+    family: str = ''   # conv rows of one family share weight set, predicate and options: offered together
+    weights: int = 0   # conv: the weight set it reads, an index into SET_KWARGS
+    variant: int = 0   # 'fixed' rows: the kernel's variant argument
+    also: int = 0      # E_* options it carries beyond bias / ReLU / BN statistics / BNB / BNP
+    grp: object = None   # its grouped launcher (conv_fwd_grp), if it has one
+    pool: bool = False   # ... whose epilogue can write the 2x2 max-pool
+
+
+E_LRELU, E_PRO, E_DIRECT = 1, 2, 4   # leaky-ReLU epilogue, normalise-on-load; E_DIRECT: no row carries it
+SLOTS = {   # what cfg[1], cfg[2] of a row's candidates hold -> the keyword arguments of its wrapper they become
+    'fixed: 0, 1': lambda r, cfg: {'variant': r.variant},
+    '0, K splits': lambda r, cfg: {'splits': cfg[2]},
+    'kernel variant, K splits': lambda r, cfg: {'variant': cfg[1], 'splits': cfg[2]},
+    'sgemm tile code, ring depth': lambda r, cfg: {'tile': cfg[1], 'nst': cfg[2]},
+    'x6p code, K splits': lambda r, cfg: dict(zip(('tile', 'nst'), x6p_unpack(cfg[1])), splits=cfg[2]),
+}
+_SGEMM, _X6P = 'sgemm tile code, ring depth', 'x6p code, K splits'
+
+
+def _fused(id, name, variant, kernel, **kw):
+    return Route(id, name, 'fixed: 0, 1', kernel, cfgs=((id, 0, 1),), variant=variant, **kw)
+
+
+_F2 = dict(family='f2', weights=0, offer=lambda H, W, C, N: wino_ok(H, W, C), grp=wino_conv_grp)
+_F4 = dict(family='f4', weights=1, offer=lambda H, W, C, N: wino4_ok(H, W, C), grp=wino4_conv_grp, pool=True)
+_F4B = dict(family='f4b', weights=3, offer=_F4['offer'], also=E_PRO)
+WINO4_PT, WINO4_PTX = -14, -15
+WINO_WGRAD, WINO4_WGRAD, WINO4_WGRAD_PT, WINO4_WGRAD_PTX = -3, -7, -13, -16
+WINO4_PTX_CFGS = tuple((WINO4_PTX, x6p_pack(t, n), s) for t, n, s in _XP_CFGS) if USE_X6P else ()
+CONV_ROUTES = {r.id: r for r in (
+    # fused F(2x2,3x3): rk_wino_conv (variants 0 / 1) and the 16x16-wave-tile kernels of winograd4.hip (2-5)
+    _fused(-1, 'F(2x2) 4-wave 64x32', 0, wino_conv, **_F2),
+    _fused(-2, 'F(2x2) 8-wave 64x64', 1, wino_conv, **_F2),
+    _fused(-8, 'F(2x2) 4-wave 32x32', 2, wino_conv, pool=True, **_F2),
+    _fused(-9, 'F(2x2) 2-wave 16x32', 3, wino_conv, pool=True, **_F2),
+    _fused(-10, 'F(2x2) 8-wave 64x32', 4, wino_conv, pool=True, **_F2),
+    # software-pipelined over two LDS stages: wins the 4x4-map layers
+    _fused(-12, 'F(2x2) 8-wave 64x32 two-stage', 5, wino_conv, pool=True, **_F2),
+    # fused F(4x4,3x3), rk_wino4_conv.  Its software-pipelined variant 2 (4-wave 32x32 over two LDS stages, one
+    # wave per SIMD) measured 1.3-1.5x slower than these on every VGG-small layer
+    # (profiles/winograd_variants_r2e.jsonl) and has no row: it stays callable as wino4_conv(variant=2) /
+    # wino4_wgrad(variant=2) for tests/test_winograd4_gpu.py
+    _fused(-5, 'F(4x4) 8-wave 64 tiles x 32 channels', 0, wino4_conv, **_F4),
+    _fused(-6, 'F(4x4) 4-wave 32 x 32', 1, wino4_conv, **_F4),
+    # the same kernel on the blocked sets (wino4b_numel); the only fused rows that normalise on load
+    _fused(-17, 'F(4x4) blocked, 8-wave tile of -5', 3, wino4_conv, **_F4B),
+    _fused(-18, 'F(4x4) blocked, 4-wave tile of -6', 4, wino4_conv, **_F4B),
+    _fused(-19, 'F(4x4) blocked, warp-specialised (4 compute + 4 loader waves, two LDS stages)', 5, wino4_conv, **_F4B),
+    # pre-transformed F(4x4) (wino4_conv_pt): on the fp32 set through sgemm_grp, on the X6 planes through x6p_gemm
+    Route(WINO4_PT, 'F(4x4) pre-transformed', _SGEMM, wino4_conv_pt, cfgs=_pt_cfgs(WINO4_PT), family='pt',
+          weights=1, offer=lambda H, W, C, N: wino4_ok(H, W, C) and wino4_pt_ok(H, W, C, N), also=E_LRELU | E_PRO),
+    Route(WINO4_PTX, 'F(4x4) pre-transformed, X6 planes', _X6P, wino4_conv_pt, cfgs=WINO4_PTX_CFGS,
+          family='ptx', weights=2, offer=lambda H, W, C, N: wino4_ptx_ok(H, W, C, N), also=E_LRELU | E_PRO),
+)}
+# weight gradients: every row's candidates depend on the problem, so ``offer`` returns them
+WGRAD_ROUTES = {r.id: r for r in (
+    Route(WINO_WGRAD, 'F(2x2) weight gradient', '0, K splits', wino_wgrad, _wino_wgrad_cands),
+    Route(WINO4_WGRAD, 'F(4x4) weight gradient', 'kernel variant, K splits', wino4_wgrad, _wino4_wgrad_cands,
+          also=E_PRO),
+    Route(WINO4_WGRAD_PT, 'F(4x4) pre-transformed weight gradient', _SGEMM, wino4_wgrad_pt, _wino4_pt_cands,
+          also=E_PRO),
+    Route(WINO4_WGRAD_PTX, 'F(4x4) pre-transformed weight gradient, X6 planes', _X6P,
+          partial(wino4_wgrad_pt, planes=True), _wino4_ptx_wgrad_cands),
+)}
+
+
+def _family(name):
+    """One conv family as a single row (what a dispatcher evaluates once per call): its first row with the
+    candidates of all its rows."""
+    rows = [r for r in CONV_ROUTES.values() if r.family == name]
+    shared = [(r.weights, r.offer, r.also, r.grp) for r in rows]
+    assert shared.count(shared[0]) == len(rows), name
+    return rows[0]._replace(name=name, cfgs=tuple(c for r in rows for c in r.cfgs))
+
+
+CONV_FAMILIES = tuple(_family(n) for n in ('f2', 'f4', 'f4b', 'pt', 'ptx'))   # the order _sets_key reads
+GRP_FAMILIES = CONV_FAMILIES[:2]   # the ones with grouped launchers
 
 
 class WinoWeights:
@@ -1163,6 +1160,10 @@ class WinoWeights:
             return None
         return lambda: self._ensure(kind, l)
 
+    def conv_sets(self, l, dgrad=False):
+        """Layer l's lazy sets as the weight-set kwargs of conv_fwd (``dgrad``: of conv_dgrad)."""
+        return conv_sets(lambda kind: self.lazy(kind, l), dgrad)
+
     def u(self, l):
         return self._view('u2', l)
 
@@ -1188,8 +1189,8 @@ class WinoWeights:
 # bias / activation / gate epilogue and the split-K combine ride in sreduce_epi / reduce_slabs
 XP_DENSE = -21
 XPD_MIN_MACS = 1 << 28   # GEMM size below which the split passes cannot pay (VGG / MLP heads, tiny layers)
-XPD_CFGS = tuple((XP_DENSE, 4 * t + n, s) for t in (0, 1, 2, 3) for n in (2, 3) for s in (1, 2, 4)) + \
-    tuple((XP_DENSE, 4 * t + 2, s) for t in (7, 8) for s in (1, 2, 4)) if USE_X6P else ()
+XPD_CFGS = tuple((XP_DENSE, x6p_pack(t, n), s) for t in (0, 1, 2, 3) for n in (2, 3) for s in (1, 2, 4)) + \
+    tuple((XP_DENSE, x6p_pack(t, 2), s) for t in (7, 8) for s in (1, 2, 4)) if USE_X6P else ()
 
 
 def _xpd(cfg):
@@ -1199,11 +1200,12 @@ def _xpd(cfg):
 def _xp_gemm_into(A, B, M, N, K, code, s, out=None, accumulate=False):
     """x6p GEMM of planes A [3][M][K] . B [3][N][K]^T: into ``out`` (s == 1) or a fresh [s][M][N] slab."""
     s = x6p_splits(K, s)
+    tile, nst = x6p_unpack(code)
     if s == 1 and out is not None:
-        x6p_gemm(A, B, out, M, N, K, tile=code // 4, nst=code % 4, accumulate=accumulate)
+        x6p_gemm(A, B, out, M, N, K, tile=tile, nst=nst, accumulate=accumulate)
         return out, 1
     slab = torch.empty((s, M, N), device=A.device, dtype=torch.float32)
-    x6p_gemm(A, B, slab, M, N, K, tile=code // 4, nst=code % 4, splits=s)
+    x6p_gemm(A, B, slab, M, N, K, tile=tile, nst=nst, splits=s)
     return slab, s
 
 
@@ -1638,12 +1640,7 @@ def s2_wgrad(x, g, *, out=None):
         slab = torch.empty((s, M, N), device=x.device, dtype=torch.float32)
         sgemm_g(7, g, x, slab, M, N, K, Co, Ci, N, *geo, tile=tile, nst=nst, splits=s, slab_stride=M * N)
         reduce_slabs(slab, out)
-    cands = _cands(M, N, splittable=True, K=K)
-    split = [c for c in cands if c[2] > 1]
-    if split:
-        cands = [max(split, key=lambda c: min(cdiv(M, tile_dims(c[0])[0]) * cdiv(N, tile_dims(c[0])[1]) * c[2],
-                                              2 * NUM_CU))] + cands
-    run(_pick(('s2w', M, N, K, H, Wd, Ci), cands, run))
+    run(_pick(('s2w', M, N, K, H, Wd, Ci), _lead_with_split(_cands(M, N, splittable=True, K=K), M, N), run))
     return out
 
 
@@ -1693,17 +1690,17 @@ def sgemm_grp(kind, A, B, out, M, N, K, lda, ldb, ldc, groups, gstride_a, gstrid
 
 
 def _grp_run(kind, A, B, out, M, N, K, lda, ldb, G, gsa, key, *, bias=None, act=ACT_NONE, slope=0.2, geo=None,
-             extra=None):
+             fused=None):
     """Autotuned grouped launch: out [G, M, N]; split-K slabs [s, G*M, N] combined by sreduce_epi with
-    per-group bias.  ``extra(cfg)``: runs the WINO_CFGS candidates (grouped Winograd convs)."""
+    per-group bias.  ``fused`` = (candidates, weight sets, epilogue): the grouped rows of CONV_ROUTES."""
     flags = _act_flags(bias, act)
     geo = geo or {}
 
     def run(cfg):
-        tile, nst, s = cfg
-        if cfg in WINO_CFGS or cfg in WINO4_CFGS:
-            extra(cfg)
+        if cfg[0] in CONV_ROUTES:
+            _run_grp_route(cfg, A, fused[1], out, fused[2])
             return
+        tile, nst, s = cfg
         if s == 1:
             sgemm_grp(kind, A, B, out, M, N, K, lda, ldb, N, G, gsa, N * K, M * N, N, tile=tile, nst=nst,
                       bias=bias, flags=flags, slope=slope, **geo)
@@ -1713,16 +1710,20 @@ def _grp_run(kind, A, B, out, M, N, K, lda, ldb, G, gsa, key, *, bias=None, act=
                   slab_stride=G * M * N, **geo)
         sreduce_epi(slab, G * M, N, out.view(G * M, N), bias=bias, act=act, slope=slope, bias_rows=M)
     cands = [c for c in _cands(M * G, N, splittable=N % 4 == 0, K=K) if (c[0] & 15) < 4 or (c[0] & 15) in _FEW_WAVE]
-    if extra is not None:
-        cands.extend(getattr(extra, 'cfgs', WINO_CFGS))
+    if fused is not None:
+        cands.extend(fused[0])
     run(_pick(key, cands, run))
     return out
 
 
+def _run_grp_route(cfg, x, sets, out, epi):
+    r = CONV_ROUTES[cfg[0]]
+    r.grp(x, sets[r.weights], out=out, variant=r.variant, **epi)
+
+
 def conv_fwd_grp_pool_ok(H, W, Cin, wino, wino4):
     """conv_fwd_grp(pool=True) has a fused candidate for this shape (F(4x4) or the small-tile F(2x2))."""
-    return ((wino4 is not None and wino4_ok(H, W, Cin))
-            or (wino is not None and wino_ok(H, W, Cin) and any(_wino_variant(c) >= 2 for c in WINO_CFGS)))
+    return any(_offered(GRP_FAMILIES, (wino, wino4), 9, H, W, Cin, 0, 0)[0])
 
 
 def conv_fwd_grp(x, W, *, bias=None, act=ACT_NONE, slope=0.2, out=None, wino=None, wino4=None, pool=False):
@@ -1743,22 +1744,14 @@ def conv_fwd_grp(x, W, *, bias=None, act=ACT_NONE, slope=0.2, out=None, wino=Non
         return _conv_fwd_grp_pooled(x, W, bias, act, out, wino, wino4)
     if out is None:
         out = torch.empty((G, Nb, H, Wd, Cout), device=x.device, dtype=torch.float32)
-    extra = None
-    w2 = wino is not None and taps == 9 and wino_ok(H, Wd, Cin) and act in (ACT_NONE, ACT_RELU)
-    w4 = wino4 is not None and taps == 9 and wino4_ok(H, Wd, Cin) and act in (ACT_NONE, ACT_RELU)
-    if w2 or w4:
-        assert not w2 or (wino.shape == (G, 16, Cout, Cin) and wino.is_contiguous())
-        assert not w4 or (wino4.shape == (G, 36, Cout, Cin) and wino4.is_contiguous())
-
-        def extra(cfg):
-            if cfg in WINO4_CFGS:
-                wino4_conv_grp(x, wino4, out=out, bias=bias, relu=act == ACT_RELU, variant=_wino4_variant(cfg))
-            else:
-                wino_conv_grp(x, wino, out=out, bias=bias, relu=act == ACT_RELU, variant=_wino_variant(cfg))
-        extra.cfgs = (WINO_CFGS if w2 else ()) + (WINO4_CFGS if w4 else ())
+    (w2, w4), cfgs = _offered(GRP_FAMILIES, (wino, wino4), taps, H, Wd, Cin, Cout,
+                              0 if act in (ACT_NONE, ACT_RELU) else E_DIRECT)
+    assert not w2 or (wino.shape == (G, 16, Cout, Cin) and wino.is_contiguous())
+    assert not w4 or (wino4.shape == (G, 36, Cout, Cin) and wino4.is_contiguous())
+    fused = (cfgs, (wino, wino4), dict(bias=bias, relu=act == ACT_RELU)) if cfgs else None
     return _grp_run(0, x, W, out, M, Cout, K, Cin, K, G, 0 if shared else M * Cin,
                     ('sfg', G, M, Cout, K, H, Wd, Cin, shared, bias is not None, act, w2, w4), bias=bias,
-                    act=act, slope=slope, geo=dict(H=H, W=Wd, C=Cin, taps=taps), extra=extra)
+                    act=act, slope=slope, geo=dict(H=H, W=Wd, C=Cin, taps=taps), fused=fused)
 
 
 def _conv_fwd_grp_pooled(x, W, bias, act, out, wino, wino4):
@@ -1767,17 +1760,17 @@ def _conv_fwd_grp_pooled(x, W, bias, act, out, wino, wino4):
     assert bias is not None and act == ACT_RELU and K == 9 * Cin and H % 2 == 0 and Wd % 2 == 0
     if out is None:
         out = torch.empty((G, Nb, H // 2, Wd // 2, Cout), device=x.device, dtype=torch.float32)
-    w4 = wino4 is not None and wino4_ok(H, Wd, Cin)
-    w2 = wino is not None and wino_ok(H, Wd, Cin)
-    cands = ([c for c in WINO4_CFGS] if w4 else []) + ([c for c in WINO_CFGS if _wino_variant(c) >= 2] if w2 else [])
+    sets = (wino, wino4)
+    w2, w4 = _offered(GRP_FAMILIES, sets, 9, H, Wd, Cin, Cout, 0)[0]
+    # the F(4x4) rows lead: the first candidate is what a capture uses on a tune miss
+    cands = [c for fam, o in (('f4', w4), ('f2', w2)) if o
+             for r in CONV_ROUTES.values() if r.family == fam and r.pool for c in r.cfgs]
     if not cands:
         raise ValueError('conv_fwd_grp(pool=True): no fused candidate (see conv_fwd_grp_pool_ok)')
+    epi = dict(bias=bias, relu=True, pool=True)
 
     def run(cfg):
-        if cfg in WINO4_CFGS:
-            wino4_conv_grp(x, wino4, out=out, bias=bias, relu=True, variant=_wino4_variant(cfg), pool=True)
-        else:
-            wino_conv_grp(x, wino, out=out, bias=bias, relu=True, variant=_wino_variant(cfg), pool=True)
+        _run_grp_route(cfg, x, sets, out, epi)
     run(_pick(('sfgp', G, Nb * H * Wd, Cout, K, H, Wd, Cin, x.dim() == 4, w2, w4), cands, run))
     return out
 

@@ -515,3 +515,95 @@ def test_conv_fwd_grp_pooled_entry_vs_fp64(H, Cin, Cout, shared):
     # per-row check too: an error confined to a few pooled pixels (a wrong window at a border) shows here
     err = (got.double().cpu() - r64.cpu()).abs().amax(-1)
     assert err.max().item() < 1e-4 * max(1.0, r64.abs().max().item()), err.max().item()
+
+
+_ROUTE_CALLS = ['fwd', 'fwd_stats', 'fwd_pro', 'dgrad', 'dgrad_bnb', 'wgrad', 'wgrad_xpro']
+_ROUTE_DATA = {}
+
+
+def _route_data():
+    """Inputs and fp64 references of test_every_offered_route, computed once (Nb=8, H=W=8, Cin=32, Cout=64:
+    the smallest shape at which every conv route id is offered)."""
+    if _ROUTE_DATA:
+        return _ROUTE_DATA
+    N, H, Cin, Cout = 8, 8, 32, 64
+    d = _ROUTE_DATA
+    d['x'], d['dy'] = _rand(N, H, H, Cin, seed=90), _rand(N, H, H, Cout, seed=91)
+    d['w'] = _rand(Cout, 3, 3, Cin, seed=92, scale=1.0 / math.sqrt(9 * Cin))
+    # rows 2 / 3 (scale, shift) are what the normalise-on-load and BN-backward epilogues read
+    d['co'] = torch.stack([_rand(Cin, seed=93), _rand(Cin, seed=94).abs() + 0.5, _rand(Cin, seed=95).abs() + 0.5,
+                           _rand(Cin, seed=96) * 0.3])
+    x64, dy64, w64 = d['x'].double(), d['dy'].double(), d['w'].double()
+    h64 = torch.relu(x64 * d['co'][2].double() + d['co'][3].double())   # the input when x is a pre-BN output
+
+    def grads(inp):
+        xi = inp.permute(0, 3, 1, 2).clone().requires_grad_(True)
+        wi = w64.permute(0, 3, 1, 2).clone().requires_grad_(True)
+        gx, gw = torch.autograd.grad(TF.conv2d(xi, wi, padding=1), (xi, wi), dy64.permute(0, 3, 1, 2))
+        return gx.permute(0, 2, 3, 1), gw.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin)
+    d['y'], d['y_pro'] = _conv_ref(d['x'], d['w'], 9), _conv_ref(h64, d['w'], 9)
+    d['gx'], d['gw'] = grads(x64)
+    d['gw_pro'] = grads(h64)[1]
+    d['gx_bnb'] = d['gx'] * (h64 > 0)   # dx masked where BN + ReLU of the input layer's y (here x) is off
+    return d
+
+
+@pytest.mark.parametrize("call", _ROUTE_CALLS)
+def test_every_offered_route(call, monkeypatch):
+    """One candidate of every route id the dispatcher offers (and its first direct-kernel candidate), run
+    through the tuning seam, against fp64 PyTorch: output and, where the epilogue forms them, the fp64
+    statistic slots, at the Winograd gate (relative L2 < 3e-5, TOL of tests/test_winograd4_gpu.py)."""
+    from rafiki_amd.ops import f32 as S
+    TOL = 3e-5
+    N, H, Cin, Cout = 8, 8, 32, 64
+    d = _route_data()
+    x, dy, co = d['x'].to(DEV), d['dy'].to(DEV), d['co'].to(DEV)
+    w2 = d['w'].to(DEV).reshape(Cout, -1).contiguous()
+    seen = {}
+
+    def grab(key, cands, run, protect=()):
+        seen['cands'], seen['run'] = list(cands), run
+        return cands[0]
+    monkeypatch.setattr(S, '_pick', grab)
+    fused = {-1, -2, -8, -9, -10, -12, -5, -6, -17, -18, -19, -14} | ({-15} if S.USE_X6P else set())
+    sums = None
+    if call.startswith('fwd'):
+        pro = call == 'fwd_pro'
+        acc = None if call == 'fwd' else torch.zeros((S.bn_slots(Cout), 2, Cout), dtype=torch.float64, device=DEV)
+        out = torch.empty((N, H, H, Cout), device=DEV)
+        S.conv_fwd(x, w2, stats_acc=acc, out=out, pro=co if pro else None, wino=lambda: S.wino_u(w2),
+                   wino4=lambda: S.wino4_u(w2), wino4p=lambda: S.wino4_u4p(w2), wino4b=lambda: S.wino4b_u(w2))
+        ref = d['y_pro'] if pro else d['y']
+        want = (fused - {-1, -2, -8, -9, -10, -12, -5, -6}) if pro else fused | {0}
+        if acc is not None:
+            r = ref.reshape(-1, Cout)
+            sums = (r.sum(0), (r * r).sum(0))
+    elif call.startswith('dgrad'):
+        acc = torch.zeros((S.bn_slots(Cin), 2, Cin), dtype=torch.float64, device=DEV) if call == 'dgrad_bnb' else None
+        out = torch.empty((N, H, H, Cin), device=DEV)
+        S.conv_dgrad(dy, S.conv_wt(w2), out=out, bnb=(x, co, acc) if acc is not None else None, wino=S.wino_ut(w2),
+                     wino4=S.wino4_ut(w2), wino4p=S.wino4_u4p(w2, dgrad=True), wino4b=S.wino4b_u(w2, dgrad=True))
+        ref, want = (d['gx_bnb'] if acc is not None else d['gx']), fused | {0}
+        if acc is not None:
+            sums = (ref.reshape(-1, Cin).sum(0), (ref * d['x'].double()).reshape(-1, Cin).sum(0))
+    else:
+        pro = call == 'wgrad_xpro'
+        acc = None
+        out = torch.empty((Cout, 9 * Cin), device=DEV)
+        S.conv_wgrad(dy, x, out=out, xpro=co if pro else None)
+        ref = d['gw_pro'] if pro else d['gw']
+        want = {-7, -13} if pro else {0, -3, -7, -13} | ({-16} if S.USE_X6P else set())
+    one = {}
+    for c in seen['cands']:
+        one.setdefault(min(c[0], 0), c)
+    assert set(one) == want, (sorted(one), sorted(want))
+    for cfg in one.values():
+        out.fill_(float('nan'))
+        if acc is not None:
+            acc.zero_()
+        seen['run'](cfg)
+        torch.cuda.synchronize()
+        e = rel(out, ref)
+        es = [rel(a, b) for a, b in zip(acc.sum(0), sums)] if sums else []
+        print(call, cfg, 'rel', e, 'sums', es)
+        assert e < TOL and all(v < TOL for v in es), (cfg, e, es)

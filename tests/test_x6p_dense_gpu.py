@@ -29,7 +29,7 @@ def _force(monkeypatch, key, cfg):
 
 def _cfgs():
     from rafiki_amd.ops import f32 as S
-    return [c for c in S.XPD_CFGS if c[1] in (0 * 4 + 2, 3 * 4 + 3, 7 * 4 + 2) and c[2] in (1, 4)]
+    return [c for c in S.XPD_CFGS if S.x6p_unpack(c[1]) in ((0, 2), (3, 3), (7, 2)) and c[2] in (1, 4)]
 
 
 @pytest.mark.parametrize('k', range(6))

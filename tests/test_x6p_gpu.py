@@ -186,7 +186,8 @@ def test_conv_fwd_tuner_offers_and_runs_plane_path():
     ref = S.conv_fwd(x, _w2(w))
     for cfg in S.WINO4_PTX_CFGS:
         y = torch.full_like(ref, float('nan'))
-        S.wino4_conv_pt(x, up, out=y, tile=cfg[1] // 4, nst=cfg[1] % 4, splits=cfg[2])
+        tile, nst = S.x6p_unpack(cfg[1])
+        S.wino4_conv_pt(x, up, out=y, tile=tile, nst=nst, splits=cfg[2])
         assert rel(y, ref) < TOL, cfg
 
 
