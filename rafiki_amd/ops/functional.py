@@ -236,8 +236,10 @@ _BWD_RED_CAP = 2048
 
 def bn_slots(C: int) -> int:
     """Atomic-accumulator slots for C channels (fewer adders per address; the consumers read
-    slots*2*C doubles per block, kept at 8 KiB)."""
-    return max(1, min(8, 512 // C))
+    slots*2*C doubles per block, kept at 8 KiB).  Always a power of two: the producers pick a slot
+    with ``block & (slots - 1)``."""
+    n = max(1, min(8, 512 // C))
+    return 1 << (n.bit_length() - 1)
 
 
 def bn_acc_buffer(C: int, device) -> torch.Tensor:
