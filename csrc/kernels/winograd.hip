@@ -506,18 +506,6 @@ __global__ __launch_bounds__(256) void wino_wt_kernel(const float* __restrict__ 
   wt_block(w, u, ut, Co, Ci, blockIdx.y * 32, blockIdx.x * 32, g);
 }
 
-// every layer of a network in one launch: desc[block] = (layer, co0, ci0, -); meta[layer] = (weight
-// offset in the arena, u offset or -1, ut offset or -1, Co, Ci) in floats
-__global__ __launch_bounds__(256) void wino_wt_multi_kernel(const float* __restrict__ arena, float* __restrict__ dst,
-                                                            const int4* __restrict__ desc,
-                                                            const long long* __restrict__ meta) {
-  __shared__ float g[32][9][33];
-  const int4 d = desc[blockIdx.x];
-  const long long* m = meta + 5 * d.x;
-  wt_block(arena + m[0], m[1] >= 0 ? dst + m[1] : nullptr, m[2] >= 0 ? dst + m[2] : nullptr, (int)m[3], (int)m[4],
-           d.y, d.z, g);
-}
-
 }  // namespace
 
 // dW [Co][9][Ci] (splits == 1, optionally accumulated) or per-split slabs [splits][Co][9][Ci] of the
@@ -557,15 +545,6 @@ extern "C" int rk_wino_weights(const float* w, float* u, float* ut, int Co, int 
   if (Co <= 0 || Ci <= 0 || (!u && !ut)) return RK_EBADARG;
   const dim3 grid(rk_cdiv(Ci, 32), rk_cdiv(Co, 32));
   hipLaunchKernelGGL(wino_wt_kernel, grid, dim3(256), 0, (hipStream_t)stream, w, u, ut, Co, Ci);
-  RK_LAUNCH_CHECK();
-  return RK_OK;
-}
-
-extern "C" int rk_wino_weights_multi(const float* arena, float* dst, const int* desc, int nblocks, const long long* meta,
-                                     void* stream) {
-  if (nblocks <= 0) return RK_OK;
-  hipLaunchKernelGGL(wino_wt_multi_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, arena, dst,
-                     (const int4*)desc, meta);
   RK_LAUNCH_CHECK();
   return RK_OK;
 }

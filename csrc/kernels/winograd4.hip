@@ -1017,29 +1017,6 @@ __global__ __launch_bounds__(256) void wino4_wt_kernel(const float* __restrict__
   w4_block(w, u, ut, Co, Ci, blockIdx.y * 32, blockIdx.x * 32, g);
 }
 
-// every layer in one launch: desc[block] = (layer, co0, ci0, -); meta[layer] = (weight offset in the
-// arena, u offset or -1, ut offset or -1, Co, Ci) in floats
-__global__ __launch_bounds__(256) void wino4_wt_multi_kernel(const float* __restrict__ arena, float* __restrict__ dst,
-                                                             const int4* __restrict__ desc,
-                                                             const long long* __restrict__ meta) {
-  __shared__ float g[32][9][33];
-  const int4 d = desc[blockIdx.x];
-  const long long* m = meta + 5 * d.x;
-  w4_block(arena + m[0], m[1] >= 0 ? dst + m[1] : nullptr, m[2] >= 0 ? dst + m[2] : nullptr, (int)m[3], (int)m[4],
-           d.y, d.z, g);
-}
-
-// the X6 planes of every layer in one launch: as wino4_wt_multi_kernel, offsets in bf16 elements of dst
-__global__ __launch_bounds__(256) void x6p_wt_multi_kernel(const float* __restrict__ arena, bf16* __restrict__ dst,
-                                                           const int4* __restrict__ desc,
-                                                           const long long* __restrict__ meta) {
-  __shared__ float g[32][9][33];
-  const int4 d = desc[blockIdx.x];
-  const long long* m = meta + 5 * d.x;
-  w4_block<true>(arena + m[0], m[1] >= 0 ? dst + m[1] : nullptr, m[2] >= 0 ? dst + m[2] : nullptr, (int)m[3],
-                 (int)m[4], d.y, d.z, g);
-}
-
 // element (pos, r, c) of a set with R output rows and C input columns (C % 8 == 0) in the blocked layout of
 // the fused forward kernel's weight stage: [R / 32 rounded up][C / 8][36][32][8], column swizzled
 RK_DEV long long w4b_index(int pos, int r, int c, int C) {
@@ -1132,14 +1109,6 @@ extern "C" int rk_wino4_weights(const float* w, float* u, float* ut, int Co, int
   return RK_OK;
 }
 
-// Every live Winograd weight set of a network, all families, in ONE launch: desc[block] = (meta row, co0,
-// ci0, family), family 0 F(2x2) fp32 sets, 1 F(4x4) fp32 sets, 2 F(4x4) X6 bf16 planes, 3 blocked F(4x4) fp32
-// sets of the UB fused kernels; meta rows as the
-// per-family kernels' (offsets in floats of dst, bf16 elements of dst for family 2).  Replaces three
-// launches, two of them a few dozen latency-bound blocks (profiles/vgg_small_f32_step_kernels_r4*).
-extern "C" int rk_wino_weights_all(const float* arena, float* dst, const int* desc, int nblocks,
-                                   const long long* meta, void* stream);
-
 // X6 planes u [36][3][Co][Ci] (nullable) / ut [36][3][Ci][Co] (nullable), bf16, of w [Co][9][Ci]
 extern "C" int rk_x6p_w4_weights(const float* w, void* u, void* ut, int Co, int Ci, void* stream) {
   if (Co <= 0 || Ci <= 0 || (!u && !ut)) return RK_EBADARG;
@@ -1161,29 +1130,16 @@ extern "C" int rk_wino4b_weights(const float* w, float* ub, float* utb, int Co, 
   return RK_OK;
 }
 
-extern "C" int rk_x6p_w4_weights_multi(const float* arena, void* dst, const int* desc, int nblocks,
-                                       const long long* meta, void* stream) {
-  if (nblocks <= 0) return RK_OK;
-  hipLaunchKernelGGL(x6p_wt_multi_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, arena, (bf16*)dst,
-                     (const int4*)desc, meta);
-  RK_LAUNCH_CHECK();
-  return RK_OK;
-}
-
+// Every live Winograd weight set of a network, all families, in ONE launch: desc[block] = (meta row, co0,
+// ci0, family), family 0 F(2x2) fp32 sets, 1 F(4x4) fp32 sets, 2 F(4x4) X6 bf16 planes, 3 blocked F(4x4) fp32
+// sets of the UB fused kernels; meta[row] = (weight offset in the arena, u offset or -1, ut offset or -1, Co,
+// Ci), offsets in floats of dst, bf16 elements of dst for family 2.  Replaces three
+// launches, two of them a few dozen latency-bound blocks (profiles/vgg_small_f32_step_kernels_r4*).
 extern "C" int rk_wino_weights_all(const float* arena, float* dst, const int* desc, int nblocks,
                                    const long long* meta, void* stream) {
   if (nblocks <= 0) return RK_OK;
   hipLaunchKernelGGL(wt_all_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, arena, dst, (const int4*)desc,
                      meta);
-  RK_LAUNCH_CHECK();
-  return RK_OK;
-}
-
-extern "C" int rk_wino4_weights_multi(const float* arena, float* dst, const int* desc, int nblocks,
-                                      const long long* meta, void* stream) {
-  if (nblocks <= 0) return RK_OK;
-  hipLaunchKernelGGL(wino4_wt_multi_kernel, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, arena, dst,
-                     (const int4*)desc, meta);
   RK_LAUNCH_CHECK();
   return RK_OK;
 }
@@ -1401,11 +1357,6 @@ extern "C" int rk_wino4_wgrad_pro(const float* dy, const float* x, float* out, i
                                   int splits, int accumulate, int variant, const float* xpro, void* stream) {
   if (!xpro) return RK_EBADARG;
   return wino4_wgrad_dispatch(dy, x, out, Nb, H, W, Co, Ci, splits, accumulate, variant, stream, xpro);
-}
-
-extern "C" int rk_wino4_wgrad(const float* dy, const float* x, float* out, int Nb, int H, int W, int Co, int Ci,
-                              int splits, int accumulate, void* stream) {
-  return rk_wino4_wgrad_v(dy, x, out, Nb, H, W, Co, Ci, splits, accumulate, 0, stream);
 }
 
 

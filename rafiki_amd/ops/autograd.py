@@ -192,9 +192,8 @@ def _wt(kind, w, fn):
     return get
 
 
-# producers of the Winograd-domain sets of one conv weight, by WinoWeights kind (no blocked sets here)
-_WINO_SETS = {'u2': S.wino_u, 'ut2': S.wino_ut, 'u4': S.wino4_u, 'ut4': S.wino4_ut, 'u4p': S.wino4_u4p,
-              'ut4p': lambda wd: S.wino4_u4p(wd, dgrad=True)}
+# the kinds of Winograd-domain sets produced here for one conv weight (no blocked sets here)
+_WINO_SETS = frozenset(k.name for k in S.SET_KINDS if k.kwarg != 'wino4b')
 
 
 def _wino_sets(w, wd, taps, dgrad=False):
@@ -202,7 +201,7 @@ def _wino_sets(w, wd, taps, dgrad=False):
     each set a callable, cached per weight inside ``cached_weight_transforms``."""
     if taps != 9:
         return {}
-    return S.conv_sets(lambda kind: _wt(kind, w, lambda: _WINO_SETS[kind](wd)) if kind in _WINO_SETS else None, dgrad)
+    return S.conv_sets(lambda kind: _wt(kind, w, lambda: S.wino_set(kind, wd)) if kind in _WINO_SETS else None, dgrad)
 
 
 # Observer of in-place gradient writes: GRAD_WATCH[0](leaf) is called right before a backward enqueues a

@@ -159,14 +159,70 @@ def _slots_flags(acc):
 # ------------------------------------------------------------------------------------------ conv
 # cfg[0] >= 0 is the direct implicit-GEMM kernel, cfg = (tile code, ring depth, K splits); cfg[0] < 0 names a
 # route of CONV_ROUTES / WGRAD_ROUTES (the route table below), which also says what cfg[1:] hold.
-SET_KWARGS = ('wino', 'wino4', 'wino4p', 'wino4b')   # the weight-set kwargs of conv_fwd / conv_dgrad
-_SET_KINDS = (('u2', 'u4', 'u4p', 'u4b'), ('ut2', 'ut4', 'ut4p', 'ut4b'))   # their WinoWeights kinds (fwd, dgrad)
+# The Winograd weight sets those routes read are the rows of SET_KINDS, one per kind.
+class SetKind(NamedTuple):
+    """One kind of Winograd weight set of a 3x3 conv weight [Cout, 3, 3, Cin].  rows, cols = (Cout, Cin) for a
+    forward kind and (Cin, Cout) for a data-gradient kind (the same conv on the flipped, transposed filters)."""
+    name: str
+    kwarg: str       # the keyword of conv_fwd / conv_dgrad it feeds
+    dgrad: bool      # the data-gradient set of its family (else the forward set)
+    family: int      # its kernel family: what rk_wino_weights_all reads in a block's fourth desc field
+    entry: str       # the single-layer entry point: (w, forward set, data-gradient set, Cout, Cin, stream)
+    size: object     # size(rows, cols): its floats of WinoWeights.buf
+    view: object     # view(flat, rows, cols): the set as the conv takes it, of its flat fp32 slice
+    unit: int        # the refresh table's offset unit per float (2: bf16 elements)
+    offered: object  # offered(f4, hw, rows, cols): a layer with hw x hw maps (None: any) gets this kind
+    padded: bool = False   # it has padding the transform never writes: its buffer starts zeroed
+
+
+def _set_pair(fwd, dgrad, kwarg, *fields, **kw):
+    """The forward and the data-gradient row of one family: they differ in name and ``dgrad`` only."""
+    return SetKind(fwd, kwarg, False, *fields, **kw), SetKind(dgrad, kwarg, True, *fields, **kw)
+
+
+def _f4_map(f4, hw):
+    return bool(f4) and (hw is None or hw % 4 == 0)
+
+
+SET_KINDS = (   # WinoWeights lays a layer's sets out in this order
+    # F(2x2,3x3) fp32 sets [16][rows][cols]
+    *_set_pair('u2', 'ut2', 'wino', 0, 'rk_wino_weights', lambda r, c: 16 * r * c,
+               lambda flat, r, c: flat.view(16, r, c), 1, lambda f4, hw, r, c: True),
+    # F(4x4,3x3) fp32 sets [36][rows][cols]: maps in multiples of 4
+    *_set_pair('u4', 'ut4', 'wino4', 1, 'rk_wino4_weights', lambda r, c: 36 * r * c,
+               lambda flat, r, c: flat.view(36, r, c), 1, lambda f4, hw, r, c: _f4_map(f4, hw)),
+    # their X6 planes, bf16 [36][3][rows][cols] (54 floats per weight), where the pre-split PT path takes the shape
+    *_set_pair('u4p', 'ut4p', 'wino4p', 2, 'rk_x6p_w4_weights', lambda r, c: 54 * r * c,
+               lambda flat, r, c: flat.view(torch.bfloat16).view(36, 3, r, c), 2,
+               lambda f4, hw, r, c: _f4_map(f4, hw) and (hw is None or wino4_ptx_ok(hw, hw, c, r))),
+    # blocked sets of the UB fused kernels, flat (wino4b_numel): columns in multiples of 8, rows padded to 32
+    *_set_pair('u4b', 'ut4b', 'wino4b', 3, 'rk_wino4b_weights', lambda r, c: wino4b_numel(r, c),
+               lambda flat, r, c: flat, 1, lambda f4, hw, r, c: _f4_map(f4, hw) and c % 8 == 0, padded=True),
+)
+KIND = {k.name: k for k in SET_KINDS}
+SET_KWARGS = tuple(k.kwarg for k in SET_KINDS if not k.dgrad)   # the weight-set kwargs of conv_fwd / conv_dgrad
 
 
 def conv_sets(lazy, dgrad=False):
     """The weight-set kwargs of conv_fwd (``dgrad``: conv_dgrad) from ``lazy(kind)``: a callable producing
-    the WinoWeights-kind set, or None where the layer has none."""
-    return {kw: lazy(kind) for kw, kind in zip(SET_KWARGS, _SET_KINDS[bool(dgrad)])}
+    the set of that kind, or None where the layer has none."""
+    return {k.kwarg: lazy(k.name) for k in SET_KINDS if k.dgrad == bool(dgrad)}
+
+
+def _set_dims(k, Cout, Cin):
+    return (Cin, Cout) if k.dgrad else (Cout, Cin)
+
+
+def wino_set(kind: str, w: torch.Tensor) -> torch.Tensor:
+    """The ``kind`` set (a SET_KINDS name) of one conv weight [Cout, 3, 3, Cin], in a fresh buffer."""
+    k = KIND[kind]
+    Cout = w.shape[0]
+    Cin = w.numel() // (9 * Cout)
+    rows, cols = _set_dims(k, Cout, Cin)
+    flat = (torch.zeros if k.padded else torch.empty)(k.size(rows, cols), device=w.device, dtype=torch.float32)
+    out = k.view(flat, rows, cols)
+    _lib.call(k.entry, _p(w), None if k.dgrad else _p(out), _p(out) if k.dgrad else None, Cout, Cin, _s())
+    return out
 
 
 def _offered(families, sets, taps, H, W, C, N, need):
@@ -420,20 +476,12 @@ def wino_weights(w: torch.Tensor, u: torch.Tensor, ut: Optional[torch.Tensor] = 
 
 def wino_u(w: torch.Tensor) -> torch.Tensor:
     """Forward Winograd weights [16][Cout][Cin] of one conv weight [Cout, 3, 3, Cin] (fresh buffer)."""
-    Cout = w.shape[0]
-    u = torch.empty((16, Cout, w.numel() // (9 * Cout)), device=w.device, dtype=torch.float32)
-    _lib.call("rk_wino_weights", _p(w), _p(u), None, Cout, u.shape[2], _s())
-    return u
+    return wino_set('u2', w)
 
 
 def wino_ut(w: torch.Tensor) -> torch.Tensor:
     """Data-gradient Winograd weights [16][Cin][Cout] of one conv weight [Cout, 3, 3, Cin]."""
-    Cout = w.shape[0]
-    Cin = w.numel() // (9 * Cout)
-    u = torch.empty((16, Cout, Cin), device=w.device, dtype=torch.float32)
-    ut = torch.empty((16, Cin, Cout), device=w.device, dtype=torch.float32)
-    _lib.call("rk_wino_weights", _p(w), _p(u), _p(ut), Cout, Cin, _s())
-    return ut
+    return wino_set('ut2', w)
 
 
 def _wino_epilogue(out, bias, stats, relu, bnb, bnp):
@@ -500,20 +548,12 @@ def bn_on_load_ok(Nb: int, H: int, W: int, Cin: int, Cout: int) -> bool:
 
 def wino4_u(w: torch.Tensor) -> torch.Tensor:
     """Forward F(4x4) weights [36][Cout][Cin] of one conv weight [Cout, 3, 3, Cin] (fresh buffer)."""
-    Cout = w.shape[0]
-    Cin = w.numel() // (9 * Cout)
-    u = torch.empty((36, Cout, Cin), device=w.device, dtype=torch.float32)
-    _lib.call("rk_wino4_weights", _p(w), _p(u), None, Cout, Cin, _s())
-    return u
+    return wino_set('u4', w)
 
 
 def wino4_ut(w: torch.Tensor) -> torch.Tensor:
     """Data-gradient F(4x4) weights [36][Cin][Cout] (flipped, transposed filters) of w [Cout, 3, 3, Cin]."""
-    Cout = w.shape[0]
-    Cin = w.numel() // (9 * Cout)
-    ut = torch.empty((36, Cin, Cout), device=w.device, dtype=torch.float32)
-    _lib.call("rk_wino4_weights", _p(w), None, _p(ut), Cout, Cin, _s())
-    return ut
+    return wino_set('ut4', w)
 
 
 # blocked F(4x4) sets: the weights as the fused kernel's LDS stage image, one contiguous 36-KiB block per 32
@@ -525,12 +565,7 @@ def wino4b_numel(N: int, C: int) -> int:
 
 def wino4b_u(w: torch.Tensor, dgrad: bool = False) -> torch.Tensor:
     """Blocked F(4x4) set (forward, or the data-gradient one) of one conv weight [Cout, 3, 3, Cin]."""
-    Cout = w.shape[0]
-    Cin = w.numel() // (9 * Cout)
-    n = wino4b_numel(Cin, Cout) if dgrad else wino4b_numel(Cout, Cin)
-    ub = torch.zeros(n, device=w.device, dtype=torch.float32)
-    _lib.call("rk_wino4b_weights", _p(w), None if dgrad else _p(ub), _p(ub) if dgrad else None, Cout, Cin, _s())
-    return ub
+    return wino_set('ut4b' if dgrad else 'u4b', w)
 
 
 def wino4_conv(x: torch.Tensor, u: torch.Tensor, *, out=None, bias=None, stats=None, relu=False, bnb=None, bnp=None,
@@ -826,11 +861,7 @@ def x6p_splits(K: int, s: int) -> int:
 def wino4_u4p(w: torch.Tensor, dgrad: bool = False) -> torch.Tensor:
     """X6 planes of the F(4x4) weights of one conv weight [Cout, 3, 3, Cin] (fresh buffer): forward set
     [36][3][Cout][Cin] (WinoWeights 'u4p'), ``dgrad``: the data-gradient set [36][3][Cin][Cout] ('ut4p')."""
-    Cout = w.shape[0]
-    Cin = w.numel() // (9 * Cout)
-    out = torch.empty((36, 3, Cin, Cout) if dgrad else (36, 3, Cout, Cin), device=w.device, dtype=torch.bfloat16)
-    _lib.call("rk_x6p_w4_weights", _p(w), None if dgrad else _p(out), _p(out) if dgrad else None, Cout, Cin, _s())
-    return out
+    return wino_set('ut4p' if dgrad else 'u4p', w)
 
 
 def wino4_ptx_ok(H, W, C, N):
@@ -1003,18 +1034,17 @@ GRP_FAMILIES = CONV_FAMILIES[:2]   # the ones with grouped launchers
 
 
 class WinoWeights:
-    """Winograd-domain weights of several 3x3 convs whose fp32 weights live in one arena: per layer the
-    F(2x2) sets u2 [16][Cout][Cin] (forward) and ut2 [16][Cin][Cout] (data gradient, ``dgrad=True``)
-    and, for maps in multiples of 4 (``f4``), the F(4x4) sets u4 [36][Cout][Cin] / ut4 [36][Cin][Cout].
+    """Winograd-domain weights of several 3x3 convs whose fp32 weights live in one arena: per layer every
+    kind of set (SET_KINDS) the layer is offered, the data-gradient kinds with ``dgrad=True``, in one buffer.
 
-    ``refresh()`` transforms every LIVE set in at most two launches per weight update.  The convs take
+    ``refresh()`` transforms every LIVE set in one launch per weight update.  The convs take
     the sets through ``lazy(kind, l)`` callables, which the autotuned conv calls only when a Winograd
     candidate of that kind runs: a set that is not fresh this step is transformed on demand (always
     correct), and ``end_step()`` narrows the live sets to the ones the tuned convs actually used, so a
     step pays only for the transforms it needs (outside graph capture; the captured step replays the
     narrowed refresh)."""
 
-    KINDS = ('u2', 'ut2', 'u4', 'ut4', 'u4p', 'ut4p', 'u4b', 'ut4b')
+    KINDS = tuple(k.name for k in SET_KINDS)
 
     def __init__(self, arena: torch.Tensor, weights, dgrad=True, f4=None, hw=None):
         """hw[l]: the layer's map size (F(4x4) sets only where it is a multiple of 4; None: every layer)."""
@@ -1029,82 +1059,44 @@ class WinoWeights:
             so = (w.data_ptr() - arena.data_ptr()) // 4
             assert 0 <= so and so + w.numel() <= arena.numel() and w.is_contiguous()
             self._layers.append((so, Cout, Cin))
-            kinds = ['u2'] + (['ut2'] if dgrad else [])
-            if f4 and (hw is None or hw[l] % 4 == 0):
-                kinds += ['u4'] + (['ut4'] if dgrad else [])
-                # X6 planes (bf16 [36][3][..], 54 floats per weight) where the pre-split PT path takes the shape
-                if hw is None or wino4_ptx_ok(hw[l], hw[l], Cin, Cout):
-                    kinds.append('u4p')
-                if dgrad and (hw is None or wino4_ptx_ok(hw[l], hw[l], Cout, Cin)):
-                    kinds.append('ut4p')
-                # blocked sets of the UB fused kernels (input columns in multiples of 8)
-                if Cin % 8 == 0:
-                    kinds.append('u4b')
-                if dgrad and Cout % 8 == 0:
-                    kinds.append('ut4b')
-            for k in kinds:
-                if k == 'u4b':
-                    n = wino4b_numel(Cout, Cin)
-                elif k == 'ut4b':
-                    n = wino4b_numel(Cin, Cout)
-                else:
-                    n = 54 * Cout * Cin if k.endswith('p') else (16 if k.endswith('2') else 36) * Cout * Cin
-                self._sets[(k, l)] = (off, n)
-                off += n
-        dev = arena.device
-        self.buf = torch.zeros(max(off, 1), dtype=torch.float32, device=dev)
+            for k in SET_KINDS:
+                rows, cols = _set_dims(k, Cout, Cin)
+                if (dgrad or not k.dgrad) and k.offered(f4, None if hw is None else hw[l], rows, cols):
+                    self._sets[(k.name, l)] = (off, k.size(rows, cols))
+                    off += k.size(rows, cols)
+        self.buf = torch.zeros(max(off, 1), dtype=torch.float32, device=arena.device)
         self._tables = {}
         self.live = frozenset(self._sets)
         self._fresh = set()
         self._used = set()
         self._prepare(self.live)
 
-    # ---- transform tables: one (desc, meta) pair per kernel family for a set of live sets
     def _prepare(self, live):
-        if live in self._tables:
-            return self._tables[live]
-        out = []
-        for fam, (ka, kb) in (('2', ('u2', 'ut2')), ('4', ('u4', 'ut4')), ('p', ('u4p', 'ut4p')), ('b', ('u4b', 'ut4b'))):
-            scale = 2 if fam == 'p' else 1   # plane sets: offsets in bf16 elements
-            meta, desc, idx = [], [], {}
-            for l, (so, Cout, Cin) in enumerate(self._layers):
-                u = self._sets.get((ka, l)) if (ka, l) in live else None
-                ut = self._sets.get((kb, l)) if (kb, l) in live else None
-                if u is None and ut is None:
-                    continue
-                idx[l] = len(meta)
-                meta.append([so, scale * u[0] if u else -1, scale * ut[0] if ut else -1, Cout, Cin])
-                for co0 in range(0, Cout, 32):
-                    for ci0 in range(0, Cin, 32):
-                        desc.append([idx[l], co0, ci0, 0])
-            if desc:
-                dev = self.arena.device
-                out.append((fam, torch.tensor(desc, dtype=torch.int32, device=dev).reshape(-1),
-                            torch.tensor(meta, dtype=torch.int64, device=dev).reshape(-1), len(desc)))
-        self._tables[live] = out
-        # every family in one table for the single-launch refresh (rk_wino_weights_all): meta rows
-        # concatenated, each block's desc row = (meta row, co0, ci0, family)
-        fam_id = {'2': 0, '4': 1, 'p': 2, 'b': 3}
-        adesc, ameta, base = [], [], 0
-        for fam, desc, meta, nb in out:
-            d = desc.view(-1, 4).cpu().clone()
-            d[:, 0] += base
-            d[:, 3] = fam_id[fam]
-            adesc.append(d)
-            ameta.append(meta.view(-1, 5).cpu())
-            base += ameta[-1].shape[0]
-        if adesc:
+        """The table rk_wino_weights_all transforms the ``live`` sets by, (desc, meta, nblocks), or None for no
+        set.  meta has one row per (family, layer) with a live set: (weight offset in the arena, forward set's
+        offset in buf or -1, data-gradient set's or -1, Cout, Cin); desc one row per 32 x 32 filter block of
+        it: (meta row, co0, ci0, family)."""
+        if live not in self._tables:
+            desc, meta = [], []
+            for fam in sorted({k.family for k in SET_KINDS}):
+                for l, (so, Cout, Cin) in enumerate(self._layers):
+                    offs = {k.dgrad: k.unit * self._sets[(k.name, l)][0]
+                            for k in SET_KINDS if k.family == fam and (k.name, l) in live}
+                    if not offs:
+                        continue
+                    desc += [[len(meta), co0, ci0, fam] for co0 in range(0, Cout, 32) for ci0 in range(0, Cin, 32)]
+                    meta.append([so, offs.get(False, -1), offs.get(True, -1), Cout, Cin])
             dev = self.arena.device
-            self._tables[('all', live)] = (torch.cat(adesc).to(dev).reshape(-1), torch.cat(ameta).to(dev).reshape(-1),
-                                           sum(int(t.shape[0]) for t in adesc))
-        return out
+            self._tables[live] = (torch.tensor(desc, dtype=torch.int32, device=dev).reshape(-1),
+                                  torch.tensor(meta, dtype=torch.int64, device=dev).reshape(-1),
+                                  len(desc)) if desc else None
+        return self._tables[live]
 
     def refresh(self):
         """Every live set of every family in ONE launch (rk_wino_weights_all)."""
-        self._prepare(self.live)
-        allt = self._tables.get(('all', self.live))
-        if allt is not None:
-            desc, meta, nb = allt
+        table = self._prepare(self.live)
+        if table is not None:
+            desc, meta, nb = table
             _lib.call("rk_wino_weights_all", _p(self.arena), _p(self.buf), _p(desc), nb, _p(meta), _s())
         self._fresh = set(self.live)
 
@@ -1123,30 +1115,15 @@ class WinoWeights:
 
     def _view(self, kind, l):
         off, n = self._sets[(kind, l)]
-        _, Cout, Cin = self._layers[l]
-        if kind in ('u4b', 'ut4b'):
-            return self.buf[off:off + n]
-        if kind.endswith('p'):
-            flat = self.buf[off:off + n].view(torch.bfloat16)
-            return flat.view((36, 3, Cout, Cin) if kind == 'u4p' else (36, 3, Cin, Cout))
-        pos = 16 if kind.endswith('2') else 36
-        shape = (pos, Cout, Cin) if kind.startswith('u') and not kind.startswith('ut') else (pos, Cin, Cout)
-        return self.buf[off:off + n].view(shape)
+        return KIND[kind].view(self.buf[off:off + n], *_set_dims(KIND[kind], *self._layers[l][1:]))
 
     def _ensure(self, kind, l):
         if (kind, l) not in self._fresh:   # not refreshed this step: transform this layer's set now
+            k = KIND[kind]
             so, Cout, Cin = self._layers[l]
             w = self.arena[so:so + 9 * Cout * Cin]
-            v = self._view(kind, l)
-            name = "rk_wino_weights" if kind.endswith('2') else "rk_wino4_weights"
-            if kind.endswith('p'):
-                name = "rk_x6p_w4_weights"
-            if kind.endswith('b'):
-                name = "rk_wino4b_weights"
-            if kind.startswith('ut'):
-                _lib.call(name, _p(w), None, _p(v), Cout, Cin, _s())
-            else:
-                _lib.call(name, _p(w), _p(v), None, Cout, Cin, _s())
+            v = _p(self._view(kind, l))
+            _lib.call(k.entry, _p(w), None if k.dgrad else v, v if k.dgrad else None, Cout, Cin, _s())
             self._fresh.add((kind, l))
         self._used.add((kind, l))
         return self._view(kind, l)

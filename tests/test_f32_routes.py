@@ -33,7 +33,7 @@ from rafiki_amd.ops import _lib, autotune, functional  # noqa: E402
 from rafiki_amd.ops import f32 as S  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'f32_routes.json')
-SEED = os.path.join(autotune.SHIPPED_DIR, 'gfx950-sd24654ad792.json')
+SEED = os.path.join(autotune.SHIPPED_DIR, 'gfx950-sa5784b06d01.json')
 F64, BF16 = torch.float64, torch.bfloat16
 
 

@@ -36,14 +36,16 @@ def _setup(monkeypatch, capturing=False):
 
 
 def _tables(ww):
-    """{family: {layer: (u_offset, ut_offset)}} of the tables refresh() launches with."""
+    """{family id: {layer: (u_offset, ut_offset)}} of the table refresh() launches with."""
     out = {}
     layer_of = {so: l for l, (so, _, _) in enumerate(ww._layers)}
-    for fam, desc, meta, nb in ww._prepare(ww.live):
-        m = meta.view(-1, 5)
-        rows = sorted({int(x) for x in desc.view(-1, 4)[:, 0]})   # meta rows the blocks point at
-        assert rows == list(range(m.shape[0])) and nb == desc.view(-1, 4).shape[0]
-        out[fam] = {layer_of[int(m[r, 0])]: (int(m[r, 1]), int(m[r, 2])) for r in rows}
+    desc, meta, nb = ww._prepare(ww.live)
+    d, m = desc.view(-1, 4), meta.view(-1, 5)
+    rows = sorted({int(x) for x in d[:, 0]})   # meta rows the blocks point at
+    assert rows == list(range(m.shape[0])) and nb == d.shape[0]
+    for r in rows:
+        (fam,) = {int(f) for f in d[d[:, 0] == r][:, 3]}   # one family per meta row
+        out.setdefault(fam, {})[layer_of[int(m[r, 0])]] = (int(m[r, 1]), int(m[r, 2]))
     return out
 
 
@@ -72,14 +74,14 @@ def test_refresh_narrows_to_the_sets_a_step_used(monkeypatch):
     ww.end_step()
     assert ww.live == frozenset({('u4', 0), ('ut2', 2)})
     t = _tables(ww)
-    assert set(t) == {'2', '4'}
+    assert set(t) == {0, 1}                                        # families F(2x2), F(4x4)
     # the plane family's meta rows carry offsets in bf16 elements (twice the float offset)
     ww.live = frozenset({('u4p', 0), ('ut4p', 0)})
-    tp = _tables(ww)['p']
+    tp = _tables(ww)[2]
     assert tp == {0: (2 * ww._sets[('u4p', 0)][0], 2 * ww._sets[('ut4p', 0)][0])}
     ww.live = frozenset({('u4', 0), ('ut2', 2)})
-    assert t['2'] == {2: (-1, ww._sets[('ut2', 2)][0])}          # gradient set only
-    assert t['4'] == {0: (ww._sets[('u4', 0)][0], -1)}           # forward set only
+    assert t[0] == {2: (-1, ww._sets[('ut2', 2)][0])}          # gradient set only
+    assert t[1] == {0: (ww._sets[('u4', 0)][0], -1)}           # forward set only
     rec.calls.clear()
     ww.refresh()
     assert rec.names() == ['rk_wino_weights_all']
@@ -120,27 +122,31 @@ def test_sconvwt_refresh_is_lazy(monkeypatch):
 
 
 def test_single_launch_refresh_table_covers_every_family(monkeypatch):
-    """One rk_wino_weights_all launch whose table is the per-family tables concatenated — meta rows
-    renumbered, the family id in each block's 4th field."""
+    """One rk_wino_weights_all launch whose table holds every family: meta rows family-major, one per (family,
+    layer) with a live half; per meta row one desc row per 32 x 32 filter block, the family id in its 4th field."""
     rec, ww = _setup(monkeypatch)
     ww.refresh()
     assert rec.names() == ['rk_wino_weights_all']
-    fams = ww._prepare(ww.live)
-    desc, meta, nb = ww._tables[('all', ww.live)]
+    desc, meta, nb = ww._prepare(ww.live)
+    assert rec.calls[0][1][2:5] == (desc.data_ptr(), nb, meta.data_ptr())   # (arena, buf, desc, nb, meta, stream)
     d, m = desc.view(-1, 4), meta.view(-1, 5)
-    assert nb == d.shape[0] == sum(f[3] for f in fams)
-    assert m.shape[0] == sum(f[2].numel() // 5 for f in fams)
-    fam_of = {'2': 0, '4': 1, 'p': 2, 'b': 3}
-    row = 0
-    base = 0
-    for fam, fdesc, fmeta, fnb in fams:
-        fd = fdesc.view(-1, 4)
-        got = d[row:row + fnb]
-        assert (got[:, 0] == fd[:, 0] + base).all() and (got[:, 1:3] == fd[:, 1:3]).all()
-        assert (got[:, 3] == fam_of[fam]).all()
-        assert torch.equal(m[base:base + fmeta.numel() // 5], fmeta.view(-1, 5))
-        row += fnb
-        base += fmeta.numel() // 5
+    assert nb == d.shape[0]
+    families = [(0, 1, ('u2', 'ut2')), (1, 1, ('u4', 'ut4')), (2, 2, ('u4p', 'ut4p')), (3, 1, ('u4b', 'ut4b'))]
+    want = []   # (family, meta row): exactly the (family, layer) pairs with a live half, -1 for a missing half
+    for fam, unit, kinds in families:   # unit 2: plane offsets in bf16 elements
+        for l, (so, Cout, Cin) in enumerate(ww._layers):
+            offs = [unit * ww._sets[(k, l)][0] if ww.has(k, l) else -1 for k in kinds]
+            if offs != [-1, -1]:
+                want.append((fam, [so] + offs + [Cout, Cin]))
+    assert m.tolist() == [row for _, row in want]
+    assert sorted({fam for fam, _ in want}) == [0, 1, 2, 3]
+    at = 0
+    for r, (fam, (_, _, _, Cout, Cin)) in enumerate(want):
+        blocks = [[r, co0, ci0, fam] for co0 in range(0, Cout, 32) for ci0 in range(0, Cin, 32)]
+        assert len(blocks) == -(-Cout // 32) * -(-Cin // 32)
+        assert d[at:at + len(blocks)].tolist() == blocks
+        at += len(blocks)
+    assert at == nb
 
 
 # ---- per-step weight-transform cache and in-place gradient marks (ops/autograd.py), host-side logic

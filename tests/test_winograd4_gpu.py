@@ -203,6 +203,58 @@ def test_wino_weights_live_sets_and_on_demand_transform():
     assert torch.equal(ww.lazy('ut4', 2)(), S.wino4_ut(ws[2]))
 
 
+def test_wino_weights_every_kind_matches_its_producer_and_blocked_sets_are_permutations():
+    """Every kind of set a layer has (planes and blocked sets included) comes out of the one-launch refresh,
+    and out of the on-demand transform of a set that is not live, bit-equal to the stand-alone producer's;
+    a blocked set is its plain set permuted by w4b_index (winograd4.hip), zero in the rows padded up to 32.
+    (40, 24) @ 4 has partial 32-blocks both ways and padded rows in both blocked sets."""
+    from rafiki_amd.ops import f32 as S
+    producers = {'u2': S.wino_u, 'ut2': S.wino_ut, 'u4': S.wino4_u, 'ut4': S.wino4_ut, 'u4p': S.wino4_u4p,
+                 'ut4p': lambda w: S.wino4_u4p(w, dgrad=True), 'u4b': S.wino4b_u,
+                 'ut4b': lambda w: S.wino4b_u(w, dgrad=True)}
+    shapes = [(64, 32), (16, 64), (40, 24)]
+    arena = torch.zeros(sum(co * 9 * ci for co, ci in shapes) + 5, device=DEV)
+    ws, off = [], 5
+    for k, (co, ci) in enumerate(shapes):
+        w = arena[off:off + co * 9 * ci].view(co, 9 * ci)
+        w.copy_(_rand(co, 9 * ci, seed=70 + k).to(DEV))
+        ws.append(w)
+        off += co * 9 * ci
+    ww = S.WinoWeights(arena, ws, hw=[8, 6, 4])
+    have = sorted(ww.live)
+    assert {k for k, l in have if l == 0} == set(producers) and {k for k, l in have if l == 1} == {'u2', 'ut2'}
+    assert {k for k, l in have if l == 2} == {'u2', 'ut2', 'u4', 'ut4', 'u4b', 'ut4b'}
+    ww.refresh()
+    for kind, l in have:
+        assert torch.equal(ww._view(kind, l), producers[kind](ws[l])), (kind, l)
+
+    def blocked_index(rows, cols):
+        pos, r, c = torch.meshgrid(torch.arange(36), torch.arange(rows), torch.arange(cols), indexing='ij')
+        return ((((r >> 5) * (cols >> 3) + (c >> 3)) * 36 + pos) * 32 + (r & 31)) * 8 + ((c & 7) ^ ((((r & 31) >> 2) & 3) << 1))
+    for (plain, blocked), l in [(kk, l) for kk in (('u4', 'u4b'), ('ut4', 'ut4b')) for l in (0, 2)]:
+        u, ub = ww._view(plain, l).cpu(), ww._view(blocked, l).cpu()
+        _, rows, cols = u.shape
+        assert (rows, cols) == (shapes[l] if plain == 'u4' else shapes[l][::-1])
+        idx = blocked_index(rows, cols).reshape(-1)
+        assert ub.shape == (S.wino4b_numel(rows, cols),) and idx.unique().numel() == idx.numel()
+        assert torch.equal(ub[idx], u.reshape(-1)), (blocked, l)
+        rest = torch.ones(ub.numel(), dtype=torch.bool)
+        rest[idx] = False
+        assert int(rest.sum()) == 36 * (-rows % 32) * cols and not ub[rest].any(), (blocked, l)
+    # narrow to two sets, change the weights: a set outside the live group is transformed on demand
+    ww.end_step()
+    ww.refresh()
+    ww.lazy('u4', 0)()
+    ww.lazy('ut2', 2)()
+    ww.end_step()
+    assert ww.live == frozenset({('u4', 0), ('ut2', 2)})
+    for w in ws:
+        w.mul_(-0.5).add_(0.25)
+    ww.refresh()
+    assert torch.equal(ww.lazy('u4p', 0)(), S.wino4_u4p(ws[0]))
+    assert torch.equal(ww.lazy('ut4b', 2)(), S.wino4b_u(ws[2], dgrad=True))
+
+
 @pytest.mark.parametrize("N,H,W,Cin,Cout", [(16, 8, 8, 64, 128), (32, 4, 4, 256, 128), (8, 16, 16, 32, 64),
                                             (64, 4, 4, 40, 36)])   # (16x16 works too; the tuner skips it)
 @pytest.mark.parametrize("tile", [0, 3, 16, 19])   # 16, 19: the X6 K loop
