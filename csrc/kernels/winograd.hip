@@ -595,10 +595,3 @@ extern "C" int rk_wino_conv_grp(const float* x, const float* u, float* y, const 
   RK_LAUNCH_CHECK();
   return RK_OK;
 }
-
-extern "C" int rk_wino_conv(const float* x, const float* u, float* y, const float* bias, double* stats, int slotMask,
-                            const float* gate, int Nb, int H, int W, int C, int N, int flags, int variant,
-                            void* stream) {
-  return rk_wino_conv_grp(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, variant, 1, 0, 0, 0, 0,
-                          stream);
-}

@@ -1145,26 +1145,35 @@ extern "C" int rk_wino_weights_all(const float* arena, float* dst, const int* de
 }
 
 namespace {
+// what the fused forward entry points receive (W4Params is what the kernels receive): flags WF_*, ``groups``
+// convs strided by gx / gu / gy / gbias floats as in rk_wino_conv_grp, pro (nullable) as in rk_wino4_conv_grp
+struct GfwdArgs {
+  const float* x; const float* u; float* y; const float* bias; double* stats; int slotMask; const float* gate;
+  int Nb, H, W, C, N, flags, groups;
+  long long gx, gu, gy, gbias;
+  const float* pro;
+  void* stream;
+};
+
 // shared launcher of the small-wave-tile Winograd forward kernels: MO = 4 (u [36][N][C], H, W multiples
 // of 4) or MO = 2 (u [16][N][C], even H, W); T tiles x BNC channels per block of NT threads
 // PRO: normalise-on-load instantiations (flags 0 / WF_STATS only: the conv after a BN + ReLU block)
 template <int MO, int WM, int WN, int MINW, int NS = 1, bool UB = false, bool WS = false, bool PRO = false>
-int launch_gfwd(const float* x, const float* u, float* y, const float* bias, double* stats, int slotMask,
-                const float* gate, int Nb, int H, int W, int C, int N, int flags, int groups, long long gx,
-                long long gu, long long gy, long long gbias, void* stream, const float* pro = nullptr) {
+int launch_gfwd(const GfwdArgs& a) {
   constexpr int T = 16 * WM, BNC = 16 * WN, P = (MO + 2) * (MO + 2);
+  const int Nb = a.Nb, H = a.H, W = a.W, C = a.C, N = a.N, flags = a.flags, groups = a.groups;
   if (Nb <= 0 || H <= 0 || W <= 0 || (H % MO) || (W % MO) || C <= 0 || (C % KC) || N <= 0 || groups <= 0)
     return RK_EBADARG;
-  if ((flags & (WF_STATS | WF_BNB | WF_BNP)) && !stats) return RK_EBADARG;
-  if ((flags & (WF_BNB | WF_BNP)) && (!gate || !bias)) return RK_EBADARG;
-  if ((flags & WF_BIAS) && !bias) return RK_EBADARG;
+  if ((flags & (WF_STATS | WF_BNB | WF_BNP)) && !a.stats) return RK_EBADARG;
+  if ((flags & (WF_BNB | WF_BNP)) && (!a.gate || !a.bias)) return RK_EBADARG;
+  if ((flags & WF_BIAS) && !a.bias) return RK_EBADARG;
   if (groups > 1 && (flags & (WF_STATS | WF_BNB | WF_BNP))) return RK_EUNSUPPORTED;
-  if (PRO != (pro != nullptr)) return RK_EBADARG;
+  if (PRO != (a.pro != nullptr)) return RK_EBADARG;
   if ((flags & WF_POOL) && (flags != WF_POOLED || PRO || (H & 1) || (W & 1))) return RK_EUNSUPPORTED;
   if (PRO && (groups > 1 || (flags & ~WF_STATS) || C > W4_PRO_MAXC)) return RK_EUNSUPPORTED;
   W4Params p;
-  p.x = x; p.u = u; p.y = y; p.bias = bias; p.stats = stats; p.gate = gate;
-  p.pro = pro;
+  p.x = a.x; p.u = a.u; p.y = a.y; p.bias = a.bias; p.stats = a.stats; p.gate = a.gate;
+  p.pro = a.pro;
   p.Nb = Nb; p.H = H; p.W = W; p.C = C; p.N = N;
   p.TW = W / MO;
   p.THW = (H / MO) * (W / MO);
@@ -1177,15 +1186,15 @@ int launch_gfwd(const float* x, const float* u, float* y, const float* bias, dou
   p.ybytes = (flags & WF_POOL) ? 4ull * Nb * (H / 2) * (W / 2) * N : 4ull * Nb * H * W * N;
   const unsigned long long gbytes = (flags & WF_BNP) ? 4 * p.ybytes : p.ybytes;
   if (p.xbytes >= 0x7fffffffull || p.ubytes >= 0x7fffffffull || gbytes >= 0x7fffffffull) return RK_EUNSUPPORTED;
-  p.slotMask = slotMask;
+  p.slotMask = a.slotMask;
   p.flags = flags;
-  p.gx = gx; p.gu = gu; p.gy = gy; p.gbias = gbias;
+  p.gx = a.gx; p.gu = a.gu; p.gy = a.gy; p.gbias = a.gbias;
   const long long bpg = (long long)rk_cdiv(p.ntiles, T) * p.ncb;
   const long long blocks = bpg * groups;
   if (blocks >= (1LL << 31)) return RK_EBADARG;
   p.bpg = (int)bpg;
   const dim3 grid((unsigned)blocks), block(64 * WM * WN * (WS ? 2 : 1));
-  const hipStream_t st = (hipStream_t)stream;
+  const hipStream_t st = (hipStream_t)a.stream;
   if constexpr (PRO) {
     if (flags == WF_STATS)
       hipLaunchKernelGGL((wino_gfwd_kernel<MO, WM, WN, MINW, WF_STATS, NS, UB, WS, true>), grid, block, 0, st, p);
@@ -1212,93 +1221,65 @@ int launch_gfwd(const float* x, const float* u, float* y, const float* bias, dou
   RK_LAUNCH_CHECK();
   return RK_OK;
 }
+
+// one row per launch_gfwd instantiation: the kernel variant, normalise-on-load or not, and its launcher
+struct GfwdRow {
+  int variant;
+  bool pro;
+  int (*launch)(const GfwdArgs&);
+};
+
+const GfwdRow W4_ROWS[] = {   // F(4x4,3x3): u [36][N][C]
+    {0, false, launch_gfwd<4, 4, 2, 1>},      // 8 waves, 64 tiles x 32 channels (1 block per CU)
+    {1, false, launch_gfwd<4, 2, 2, 2>},      // 4 waves, 32 x 32 (2 per CU)
+    {2, false, launch_gfwd<4, 2, 2, 1, 2>},   // 4 waves, 32 x 32, two LDS stages (147 KiB), software-pipelined
+    // blocked weights (rk_wino4b_weights layout): variant 3 = variant 0's tile, 4 = variant 1's
+    {3, false, launch_gfwd<4, 4, 2, 1, 1, true>},
+    {4, false, launch_gfwd<4, 2, 2, 2, 1, true>},
+    // warp-specialised 32 x 32 (4 compute + 4 loader waves, two stages, 147 KiB), blocked weights
+    {5, false, launch_gfwd<4, 2, 2, 1, 2, true, true>},
+    // normalise-on-load: the blocked-weight tiles only (the training path's weight sets)
+    {3, true, launch_gfwd<4, 4, 2, 1, 1, true, false, true>},
+    {4, true, launch_gfwd<4, 2, 2, 2, 1, true, false, true>},
+    {5, true, launch_gfwd<4, 2, 2, 1, 2, true, true, true>},
+};
+
+const GfwdRow W2S_ROWS[] = {   // F(2x2,3x3): u [16][N][C]
+    {0, false, launch_gfwd<2, 2, 2, 3>},      // 4 waves, 32 tiles x 32 channels (32 KiB LDS, 3 blocks per CU)
+    {1, false, launch_gfwd<2, 1, 2, 3>},      // 2 waves, 16 x 32
+    {2, false, launch_gfwd<2, 4, 2, 2>},      // 8 waves, 64 tiles x 32 channels (48 KiB LDS)
+    {3, false, launch_gfwd<2, 4, 2, 1, 2>},   // 8 waves, 64 x 32, two LDS stages (96 KiB), software-pipelined
+};
+
+// a miss: no normalise-on-load form of that variant (RK_EUNSUPPORTED), or no such variant (RK_EBADARG)
+template <int NR>
+int gfwd_dispatch(const GfwdRow (&rows)[NR], int variant, const GfwdArgs& a) {
+  for (const GfwdRow& r : rows)
+    if (r.variant == variant && r.pro == (a.pro != nullptr)) return r.launch(a);
+  return a.pro ? RK_EUNSUPPORTED : RK_EBADARG;
+}
 }  // namespace
 
-// y = conv3x3(x, w) via F(4x4,3x3) with u = rk_wino4_weights(w); flags / grouping as rk_wino_conv_grp.
-// variant 0: 8 waves, 64 tiles x 32 channels (1 block per CU); 1: 4 waves, 32 x 32 (2 per CU)
-static int wino4_conv_dispatch(const float* x, const float* u, float* y, const float* bias, double* stats,
-                               int slotMask, const float* gate, int Nb, int H, int W, int C, int N, int flags,
-                               int variant, int groups, long long gx, long long gu, long long gy, long long gbias,
-                               void* stream, const float* pro) {
-  if (pro) {   // normalise-on-load: the blocked-weight tiles only (the training path's weight sets)
-    if (variant == 3)
-      return launch_gfwd<4, 4, 2, 1, 1, true, false, true>(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N,
-                                                           flags, groups, gx, gu, gy, gbias, stream, pro);
-    if (variant == 4)
-      return launch_gfwd<4, 2, 2, 2, 1, true, false, true>(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N,
-                                                           flags, groups, gx, gu, gy, gbias, stream, pro);
-    if (variant == 5)
-      return launch_gfwd<4, 2, 2, 1, 2, true, true, true>(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N,
-                                                          flags, groups, gx, gu, gy, gbias, stream, pro);
-    return RK_EUNSUPPORTED;
-  }
-  if (variant == 0)
-    return launch_gfwd<4, 4, 2, 1>(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, groups, gx, gu, gy,
-                                   gbias, stream);
-  if (variant == 1)
-    return launch_gfwd<4, 2, 2, 2>(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, groups, gx, gu, gy,
-                                   gbias, stream);
-  if (variant == 2)   // 4 waves, 32 x 32, two LDS stages (147 KiB), software-pipelined
-    return launch_gfwd<4, 2, 2, 1, 2>(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, groups, gx, gu,
-                                      gy, gbias, stream);
-  // blocked weights (rk_wino4b_weights layout): variant 3 = variant 0's tile, 4 = variant 1's
-  if (variant == 3)
-    return launch_gfwd<4, 4, 2, 1, 1, true>(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, groups, gx,
-                                            gu, gy, gbias, stream);
-  if (variant == 4)
-    return launch_gfwd<4, 2, 2, 2, 1, true>(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, groups, gx,
-                                            gu, gy, gbias, stream);
-  // 5: warp-specialised 32 x 32 (4 compute + 4 loader waves, two stages, 147 KiB), blocked weights
-  if (variant == 5)
-    return launch_gfwd<4, 2, 2, 1, 2, true, true>(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, groups,
-                                                  gx, gu, gy, gbias, stream);
-  return RK_EBADARG;
-}
-
+// y = conv3x3(x, w) via F(4x4,3x3) with u = rk_wino4_weights(w); flags / grouping as rk_wino_conv_grp; variants:
+// W4_ROWS.  pro (nullable), normalise-on-load: x is the pre-BN output of the previous conv and pro = its BN scale [C],
+// shift [C]; every in-image input element is loaded as relu(x * scale + shift) (the consumer of a materialised
+// BN + ReLU pass)
 extern "C" int rk_wino4_conv_grp(const float* x, const float* u, float* y, const float* bias, double* stats,
                                  int slotMask, const float* gate, int Nb, int H, int W, int C, int N, int flags,
                                  int variant, int groups, long long gx, long long gu, long long gy, long long gbias,
-                                 void* stream) {
-  return wino4_conv_dispatch(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, variant, groups, gx, gu,
-                             gy, gbias, stream, nullptr);
+                                 const float* pro, void* stream) {
+  return gfwd_dispatch(W4_ROWS, variant, {x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, groups, gx, gu,
+                                          gy, gbias, pro, stream});
 }
 
-// normalise-on-load: x is the pre-BN output of the previous conv and pro = its BN scale [C], shift [C]; every
-// in-image input element is loaded as relu(x * scale + shift) (the consumer of a materialised BN + ReLU pass)
-extern "C" int rk_wino4_conv_pro(const float* x, const float* u, float* y, const float* bias, double* stats,
-                                 int slotMask, const float* gate, int Nb, int H, int W, int C, int N, int flags,
-                                 int variant, const float* pro, void* stream) {
-  if (!pro) return RK_EBADARG;
-  return wino4_conv_dispatch(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, variant, 1, 0, 0, 0, 0,
-                             stream, pro);
-}
-
-// F(2x2,3x3) with u = rk_wino_weights(w) [16][N][C] on small wave tiles (many blocks for small grids):
-// variant 0: 4 waves, 32 tiles x 32 channels (32 KiB LDS, 3 blocks per CU); 1: 2 waves, 16 x 32
+// F(2x2,3x3) with u = rk_wino_weights(w) [16][N][C] on small wave tiles (many blocks for small grids); variants:
+// W2S_ROWS
 extern "C" int rk_wino2s_conv_grp(const float* x, const float* u, float* y, const float* bias, double* stats,
                                   int slotMask, const float* gate, int Nb, int H, int W, int C, int N, int flags,
                                   int variant, int groups, long long gx, long long gu, long long gy, long long gbias,
                                   void* stream) {
-  if (variant == 0)
-    return launch_gfwd<2, 2, 2, 3>(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, groups, gx, gu, gy,
-                                   gbias, stream);
-  if (variant == 1)
-    return launch_gfwd<2, 1, 2, 3>(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, groups, gx, gu, gy,
-                                   gbias, stream);
-  if (variant == 2)   // 8 waves, 64 tiles x 32 channels (48 KiB LDS)
-    return launch_gfwd<2, 4, 2, 2>(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, groups, gx, gu, gy,
-                                   gbias, stream);
-  if (variant == 3)   // 8 waves, 64 x 32, two LDS stages (96 KiB), software-pipelined
-    return launch_gfwd<2, 4, 2, 1, 2>(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, groups, gx, gu,
-                                      gy, gbias, stream);
-  return RK_EBADARG;
-}
-
-extern "C" int rk_wino4_conv(const float* x, const float* u, float* y, const float* bias, double* stats, int slotMask,
-                             const float* gate, int Nb, int H, int W, int C, int N, int flags, int variant,
-                             void* stream) {
-  return rk_wino4_conv_grp(x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, variant, 1, 0, 0, 0, 0,
-                           stream);
+  return gfwd_dispatch(W2S_ROWS, variant, {x, u, y, bias, stats, slotMask, gate, Nb, H, W, C, N, flags, groups, gx,
+                                           gu, gy, gbias, nullptr, stream});
 }
 
 // dW [Co][9][Ci] (splits == 1, optionally accumulated) or per-split slabs [splits][Co][9][Ci] of the
@@ -1308,8 +1289,10 @@ extern "C" int rk_wino4_conv(const float* x, const float* u, float* y, const flo
 // (A position-split variant — each wave 9 of the 36 positions for a whole 32x32 tile on 32x32x2 MFMAs,
 // half the LDS reads per MFMA cycle — measured 5-8% SLOWER than variant 1 on every VGG-small layer,
 // profiles/wgrad4_variants_r3.jsonl, and was removed: the LDS-write / transform phase bounds it.)
-static int wino4_wgrad_dispatch(const float* dy, const float* x, float* out, int Nb, int H, int W, int Co, int Ci,
-                                int splits, int accumulate, int variant, void* stream, const float* xpro) {
+// xpro (nullable), normalise-on-load: x is the pre-BN output of its producer, xpro = that BN's scale [Ci],
+// shift [Ci] (+ ReLU); variants 0 / 1
+extern "C" int rk_wino4_wgrad(const float* dy, const float* x, float* out, int Nb, int H, int W, int Co, int Ci,
+                              int splits, int accumulate, int variant, const float* xpro, void* stream) {
   if (Nb <= 0 || H <= 0 || W <= 0 || (H & 3) || (W & 3) || Co <= 0 || Ci <= 0 || splits <= 0) return RK_EBADARG;
   if (splits > 1 && accumulate) return RK_EBADARG;
   if (variant < 0 || variant > 2) return RK_EBADARG;
@@ -1346,19 +1329,6 @@ static int wino4_wgrad_dispatch(const float* dy, const float* x, float* out, int
   RK_LAUNCH_CHECK();
   return RK_OK;
 }
-
-extern "C" int rk_wino4_wgrad_v(const float* dy, const float* x, float* out, int Nb, int H, int W, int Co, int Ci,
-                                int splits, int accumulate, int variant, void* stream) {
-  return wino4_wgrad_dispatch(dy, x, out, Nb, H, W, Co, Ci, splits, accumulate, variant, stream, nullptr);
-}
-
-// normalise-on-load: x is the pre-BN output of its producer, xpro = that BN's scale [Ci], shift [Ci] (+ ReLU)
-extern "C" int rk_wino4_wgrad_pro(const float* dy, const float* x, float* out, int Nb, int H, int W, int Co, int Ci,
-                                  int splits, int accumulate, int variant, const float* xpro, void* stream) {
-  if (!xpro) return RK_EBADARG;
-  return wino4_wgrad_dispatch(dy, x, out, Nb, H, W, Co, Ci, splits, accumulate, variant, stream, xpro);
-}
-
 
 // ------------------------------------------------------------- pre-transformed weight gradient (deep layers)
 // dW by F(4x4,3x3) as three launches: transform every 4x4 dy patch (M = A dY A^T) and every 6x6 x
@@ -1728,8 +1698,9 @@ __global__ __launch_bounds__(256) void w4pt_out_kernel(const float* __restrict__
 }  // namespace
 
 // M [36][T][Co] and V [36][T][Ci] (T = Nb * H/4 * W/4 tiles) of dy / x (NHWC, H and W multiples of 4)
-static int wino4_pt_transform(const float* dy, const float* x, float* m, float* v, int Nb, int H, int W, int Co,
-                              int Ci, void* stream, const float* xpro) {
+// xpro (nullable): x normalised on load (its producer's BN scale [Ci], shift [Ci], + ReLU)
+extern "C" int rk_wino4_pt_transform(const float* dy, const float* x, float* m, float* v, int Nb, int H, int W,
+                                     int Co, int Ci, const float* xpro, void* stream) {
   if (Nb <= 0 || H <= 0 || W <= 0 || (H & 3) || (W & 3) || Co <= 0 || Ci <= 0) return RK_EBADARG;
   if ((Co & 3) || (Ci & 3)) return RK_EUNSUPPORTED;
   const int TW = W / 4, THW = (H / 4) * (W / 4);
@@ -1743,18 +1714,6 @@ static int wino4_pt_transform(const float* dy, const float* x, float* m, float* 
                      v, H, W, Ci, TW, THW, (int)tx, (int)T, xpro);
   RK_LAUNCH_CHECK();
   return RK_OK;
-}
-
-extern "C" int rk_wino4_pt_transform(const float* dy, const float* x, float* m, float* v, int Nb, int H, int W,
-                                     int Co, int Ci, void* stream) {
-  return wino4_pt_transform(dy, x, m, v, Nb, H, W, Co, Ci, stream, nullptr);
-}
-
-// the same with x normalised on load (xpro: its producer's BN scale [Ci], shift [Ci], + ReLU)
-extern "C" int rk_wino4_pt_transform_pro(const float* dy, const float* x, float* m, float* v, int Nb, int H, int W,
-                                         int Co, int Ci, const float* xpro, void* stream) {
-  if (!xpro) return RK_EBADARG;
-  return wino4_pt_transform(dy, x, m, v, Nb, H, W, Co, Ci, stream, xpro);
 }
 
 // du: nslab slabs of [36][Co][Ci], slab floats apart (split-K partial sums), summed here
@@ -2035,9 +1994,9 @@ extern "C" int rk_wino4_pt_conv_out(const float* yt, float* y, const float* bias
   return RK_OK;
 }
 
-// V = B^T x B of every 6x6 window: [36][T][C] (the x half of rk_wino4_pt_transform)
-extern "C" int rk_wino4_pt_input_pro(const float* x, float* v, int Nb, int H, int W, int C, const float* pro,
-                                     void* stream) {
+// V = B^T x B of every 6x6 window: [36][T][C] (the x half of rk_wino4_pt_transform); pro (nullable) as its xpro
+extern "C" int rk_wino4_pt_input(const float* x, float* v, int Nb, int H, int W, int C, const float* pro,
+                                 void* stream) {
   if (Nb <= 0 || H <= 0 || W <= 0 || (H & 3) || (W & 3) || C <= 0) return RK_EBADARG;
   if (C & 3) return RK_EUNSUPPORTED;
   const int TW = W / 4, THW = (H / 4) * (W / 4);
@@ -2050,13 +2009,9 @@ extern "C" int rk_wino4_pt_input_pro(const float* x, float* v, int Nb, int H, in
   return RK_OK;
 }
 
-extern "C" int rk_wino4_pt_input(const float* x, float* v, int Nb, int H, int W, int C, void* stream) {
-  return rk_wino4_pt_input_pro(x, v, Nb, H, W, C, nullptr, stream);
-}
-
 // V planes [36][3][T][C] (bf16 hi, mid, lo of B^T x B) for the pre-split X6 GEMM (x6p.hip); pro as above
-extern "C" int rk_x6p_w4_input_pro(const float* x, void* v, int Nb, int H, int W, int C, const float* pro,
-                                   void* stream) {
+extern "C" int rk_x6p_w4_input(const float* x, void* v, int Nb, int H, int W, int C, const float* pro,
+                               void* stream) {
   if (Nb <= 0 || H <= 0 || W <= 0 || (H & 3) || (W & 3) || C <= 0) return RK_EBADARG;
   if (C & 3) return RK_EUNSUPPORTED;
   const int TW = W / 4, THW = (H / 4) * (W / 4);
@@ -2077,10 +2032,6 @@ extern "C" int rk_x6p_w4_input_pro(const float* x, void* v, int Nb, int H, int W
                        (hipStream_t)stream, x, v, H, W, C, TW, THW, (int)tx, (int)T, pro);
   RK_LAUNCH_CHECK();
   return RK_OK;
-}
-
-extern "C" int rk_x6p_w4_input(const float* x, void* v, int Nb, int H, int W, int C, void* stream) {
-  return rk_x6p_w4_input_pro(x, v, Nb, H, W, C, nullptr, stream);
 }
 
 // M^T planes [36][3][Co][T] of dy and V^T planes [36][3][Ci][T] of x (bf16), the weight-gradient operands

@@ -73,20 +73,14 @@ _SIGS = {
     "rk_wino_weights": [vp, vp, vp, i32, i32, vp],
     "rk_wino_conv_grp": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, vp],
     "rk_wino_wgrad": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
-    "rk_wino_conv": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp],
     "rk_wino4_weights": [vp, vp, vp, i32, i32, vp],
     "rk_wino4b_weights": [vp, vp, vp, i32, i32, vp],
-    "rk_wino4_conv_grp": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, vp],
-    "rk_wino4_conv": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp],
-    "rk_wino4_conv_pro": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp],
-    "rk_wino4_wgrad_pro": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp],
-    "rk_wino4_pt_transform_pro": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp],
-    "rk_wino4_pt_input_pro": [vp, vp, i32, i32, i32, i32, vp, vp],
-    "rk_x6p_w4_input_pro": [vp, vp, i32, i32, i32, i32, vp, vp],
-    "rk_wino4_wgrad_v": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
-    "rk_wino4_pt_transform": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "rk_wino4_conv_grp": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, vp,
+                          vp],
+    "rk_wino4_wgrad": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp],
+    "rk_wino4_pt_transform": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp],
     "rk_wino4_pt_output": [vp, vp, i32, i32, i32, i32, i64, vp],
-    "rk_wino4_pt_input": [vp, vp, i32, i32, i32, i32, vp],
+    "rk_wino4_pt_input": [vp, vp, i32, i32, i32, i32, vp, vp],
     "rk_wino4_pt_conv_out": [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i64, i32, f32, vp],
     "rk_wino2s_conv_grp": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, vp],
     # fp32 path (sgemm.hip, bnf.hip)
@@ -137,11 +131,10 @@ _SIGS = {
     "rk_x6p_split_t": [vp, vp, i32, i32, i32, i32, i64, vp],
     "rk_x6p_w4_weights": [vp, vp, vp, i32, i32, vp],
     "rk_wino_weights_all": [vp, vp, vp, i32, vp, vp],
-    "rk_x6p_w4_input": [vp, vp, i32, i32, i32, i32, vp],
+    "rk_x6p_w4_input": [vp, vp, i32, i32, i32, i32, vp, vp],
     "rk_x6p_w4_wgrad_transform": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
 }
 
-_OPTIONAL: set[str] = set()
 # non-int return types
 _RESTYPES = {"rk_embedding_bwd_ws": (C.c_longlong, [i32])}
 
@@ -171,8 +164,6 @@ def lib():
             try:
                 fn = getattr(h, name)
             except AttributeError:
-                if name in _OPTIONAL:
-                    continue
                 raise NativeLibraryError(f"{KERNEL_LIB} lacks symbol {name}: rebuild it")
             fn.argtypes = args
             fn.restype = C.c_int

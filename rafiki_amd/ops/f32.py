@@ -487,7 +487,6 @@ def wino_ut(w: torch.Tensor) -> torch.Tensor:
 def _wino_epilogue(out, bias, stats, relu, bnb, bnp):
     """(flags, bias, stats, gate) of a Winograd conv's epilogue: bias / ReLU / BN statistics, or with ``bnb``
     / ``bnp`` = (y, coeffs, acc) the BN-backward forms of conv_dgrad (gate = y, bias = BN scale | shift)."""
-    Nb, H, W, N = out.shape
     flags = (WF_BIAS if bias is not None else 0) | (WF_RELU if relu else 0) | (WF_STATS if stats is not None else 0)
     gate = None
     if bnb is not None:
@@ -496,11 +495,50 @@ def _wino_epilogue(out, bias, stats, relu, bnb, bnp):
         bias, flags = coeffs[2:4].reshape(-1).contiguous(), WF_BNB
     elif bnp is not None:
         gate, coeffs, stats = bnp
+        Nb, H, W, N = out.shape
         assert gate.shape == (Nb, 2 * H, 2 * W, N)
         bias, flags = coeffs[2:4].reshape(-1).contiguous(), WF_BNP
     if stats is not None:
-        assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.shape[-1] == N
+        assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.shape[-1] == out.shape[-1]
     return flags, bias, stats, gate
+
+
+def _pro(pro):
+    """A kernel's nullable normalise-on-load argument: scale [C], shift [C] of the BN coeffs [4][C], or NULL."""
+    return None if pro is None else _p(pro[2])
+
+
+def _fused_conv(name, variant, x, u, out, oshape, *, bias=None, stats=None, relu=False, bnb=None, bnp=None,
+                pool=False, grp=(1, 0, 0, 0, 0), tail=()):
+    """What wino_conv, wino4_conv and their _grp forms share: ``out`` (allocated if None) of shape ``oshape``, the
+    epilogue flags and the call of the fused entry point ``name``.  grp = (groups, gx, gu, gy, gbias); ``tail``:
+    what the entry point takes between those and the stream (rk_wino4_conv_grp: pro)."""
+    Nb, H, W, C = x.shape[-4:]
+    if out is None:
+        out = torch.empty(oshape, device=x.device, dtype=torch.float32)
+    assert out.shape == oshape and out.is_contiguous()
+    flags, bias, stats, gate = _wino_epilogue(out, bias, stats, relu, bnb, bnp)
+    _lib.call(name, _p(x), _p(u), _p(out), _p(bias), _p(stats), _slots_flags(stats), _p(gate), Nb, H, W, C, oshape[-1],
+              flags | (WF_POOL if pool else 0), int(variant), *grp, *tail, _s())
+    return out
+
+
+def _grp_conv(name, variant, P, x, u, out, bias, relu, pool, tail=()):
+    """The _grp forms: G convs in one grid, x [G, Nb, H, W, C] (or shared [Nb, H, W, C]), u [G, P, N, C]."""
+    G, _, N, C = u.shape
+    shared = x.dim() == 4
+    Nb, H, W, Cx = x.shape[-4:]
+    assert Cx == C and (shared or x.shape[0] == G) and u.is_contiguous() and x.is_contiguous()
+    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
+    grp = (G, 0 if shared else Nb * H * W * C, P * N * C, Nb * Ho * Wo * N, N if bias is not None else 0)
+    return _fused_conv(name, variant, x, u, out, (G, Nb, Ho, Wo, N), bias=bias, relu=relu, pool=pool, grp=grp,
+                       tail=tail)
+
+
+def _wino2_entry(variant):
+    """(entry point, its variant) of F(2x2) variant 0-5: 2-5 are the small-wave-tile kernels of winograd4.hip
+    (small grids)."""
+    return ("rk_wino2s_conv_grp", variant - 2) if variant >= 2 else ("rk_wino_conv_grp", variant)
 
 
 def wino_conv(x: torch.Tensor, u: torch.Tensor, *, out=None, bias=None, stats=None, relu=False, bnb=None, bnp=None,
@@ -511,17 +549,8 @@ def wino_conv(x: torch.Tensor, u: torch.Tensor, *, out=None, bias=None, stats=No
     Nb, H, W, C = x.shape
     N = u.shape[1]
     assert u.shape == (16, N, C) and u.is_contiguous(), (u.shape, x.shape)
-    if out is None:
-        out = torch.empty((Nb, H, W, N), device=x.device, dtype=torch.float32)
-    assert out.shape == (Nb, H, W, N) and out.is_contiguous()
-    flags, bias, stats, gate = _wino_epilogue(out, bias, stats, relu, bnb, bnp)
-    if variant >= 2:   # the small-wave-tile F(2x2) kernels (csrc/kernels/winograd4.hip): small grids
-        _lib.call("rk_wino2s_conv_grp", _p(x), _p(u), _p(out), _p(bias), _p(stats), _slots_flags(stats), _p(gate),
-                  Nb, H, W, C, N, flags, int(variant) - 2, 1, 0, 0, 0, 0, _s())
-        return out
-    _lib.call("rk_wino_conv", _p(x), _p(u), _p(out), _p(bias), _p(stats), _slots_flags(stats), _p(gate),
-              Nb, H, W, C, N, flags, int(variant), _s())
-    return out
+    return _fused_conv(*_wino2_entry(variant), x, u, out, (Nb, H, W, N), bias=bias, stats=stats, relu=relu, bnb=bnb,
+                       bnp=bnp)
 
 
 # ----------------------------------------------------------------- Winograd F(4x4, 3x3) forward
@@ -582,18 +611,11 @@ def wino4_conv(x: torch.Tensor, u: torch.Tensor, *, out=None, bias=None, stats=N
     else:
         N = u.shape[1]
         assert u.shape == (36, N, C) and u.is_contiguous(), (u.shape, x.shape)
-    if out is None:
-        out = torch.empty((Nb, H, W, N), device=x.device, dtype=torch.float32)
-    assert out.shape == (Nb, H, W, N) and out.is_contiguous()
-    flags, bias, stats, gate = _wino_epilogue(out, bias, stats, relu, bnb, bnp)
     if pro is not None:
-        assert variant >= 3 and flags in (0, WF_STATS) and pro.shape == (4, C) and pro.is_contiguous()
-        _lib.call("rk_wino4_conv_pro", _p(x), _p(u), _p(out), None, _p(stats), _slots_flags(stats), None,
-                  Nb, H, W, C, N, flags, int(variant), _p(pro[2]), _s())
-        return out
-    _lib.call("rk_wino4_conv", _p(x), _p(u), _p(out), _p(bias), _p(stats), _slots_flags(stats), _p(gate),
-              Nb, H, W, C, N, flags, int(variant), _s())
-    return out
+        assert variant >= 3 and bias is None and not relu and bnb is None and bnp is None
+        assert pro.shape == (4, C) and pro.is_contiguous()
+    return _fused_conv("rk_wino4_conv_grp", variant, x, u, out, (Nb, H, W, N), bias=bias, stats=stats, relu=relu,
+                       bnb=bnb, bnp=bnp, tail=(_pro(pro),))
 
 
 # largest map the pre-transformed paths are offered on: 8 with the f32 GEMM (they lost on 16x16 maps,
@@ -646,19 +668,13 @@ def wino4_conv_pt(x: torch.Tensor, u: torch.Tensor, *, out=None, bias=None, stat
         # Y' tile-major [T][36][N]: the output transform reads each tile's 36 positions as one run
         yt = torch.empty((splits, T, 36, N), device=x.device, dtype=torch.float32)
         v = torch.empty((36, 3, T, C), device=x.device, dtype=torch.bfloat16)
-        if pro is None:
-            _lib.call("rk_x6p_w4_input", _p(x), _p(v), Nb, H, W, C, _s())
-        else:
-            _lib.call("rk_x6p_w4_input_pro", _p(x), _p(v), Nb, H, W, C, _p(pro[2]), _s())
+        _lib.call("rk_x6p_w4_input", _p(x), _p(v), Nb, H, W, C, _pro(pro), _s())
         x6p_gemm(v, u, yt, T, N, C, groups=36, tile=tile, nst=nst, splits=splits, row_major_groups=True)
     else:
         splits = 1
         yt = torch.empty((36, T, N), device=x.device, dtype=torch.float32)
         v = torch.empty((36, T, C), device=x.device, dtype=torch.float32)
-        if pro is None:
-            _lib.call("rk_wino4_pt_input", _p(x), _p(v), Nb, H, W, C, _s())
-        else:
-            _lib.call("rk_wino4_pt_input_pro", _p(x), _p(v), Nb, H, W, C, _p(pro[2]), _s())
+        _lib.call("rk_wino4_pt_input", _p(x), _p(v), Nb, H, W, C, _pro(pro), _s())
         sgemm_grp(KIND_DENSE, v, u, yt, T, N, C, C, C, N, 36, T * C, N * C, T * N, tile=tile, nst=nst)
     _lib.call("rk_wino4_pt_conv_out", _p(yt), _p(out), _p(bias), _p(stats), _slots_flags(stats), _p(gate),
               Nb, H, W, N, flags, splits, 36 * T * N, int(planes), float(0.0 if lrelu is None else lrelu), _s())
@@ -668,27 +684,12 @@ def wino4_conv_pt(x: torch.Tensor, u: torch.Tensor, *, out=None, bias=None, stat
 def wino4_conv_grp(x, u, *, out=None, bias=None, relu=False, variant=0, pool=False):
     """k F(4x4) convs in one grid: x [G, Nb, H, W, C] (or shared [Nb, H, W, C]), u [G, 36, N, C].
     ``pool`` (with bias + relu): the 2x2 max-pool from the epilogue, out [G, Nb, H/2, W/2, N]."""
-    G, _, N, C = u.shape
-    shared = x.dim() == 4
-    Nb, H, W, Cx = x.shape[-4:]
-    assert Cx == C and (shared or x.shape[0] == G) and u.is_contiguous() and x.is_contiguous()
-    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
-    if out is None:
-        out = torch.empty((G, Nb, Ho, Wo, N), device=x.device, dtype=torch.float32)
-    assert out.shape == (G, Nb, Ho, Wo, N) and out.is_contiguous()
-    M = Nb * H * W
-    flags = (WF_BIAS if bias is not None else 0) | (WF_RELU if relu else 0)
-    if pool:
-        assert bias is not None and relu
-        flags |= WF_POOL
-    _lib.call("rk_wino4_conv_grp", _p(x), _p(u), _p(out), _p(bias), None, 0, None, Nb, H, W, C, N, flags,
-              int(variant), G, 0 if shared else M * C, 36 * N * C, Nb * Ho * Wo * N, N if bias is not None else 0,
-              _s())
-    return out
+    assert not pool or (bias is not None and relu)
+    return _grp_conv("rk_wino4_conv_grp", variant, 36, x, u, out, bias, relu, pool, tail=(None,))
 
 
 def _wino4_wgrad_cands(Nb, H, W, Cout, Cin):
-    """Split-K choices of rk_wino4_wgrad_v (variant 0: 32 co x 32 ci blocks, 1: 64 co x 32 ci, 2: 32 x 32
+    """Split-K choices of rk_wino4_wgrad (variant 0: 32 co x 32 ci blocks, 1: 64 co x 32 ci, 2: 32 x 32
     software-pipelined over two LDS stages): 128..4096
     blocks, >= 4 chunks of 8 tiles per block, slabs <= 256 MiB.  cfg = (WINO4_WGRAD, variant, splits)."""
     if not (WINO and WINO4 and H % 4 == 0 and W % 4 == 0 and Cin >= 8 and Cout >= 16):
@@ -723,17 +724,15 @@ def wino4_wgrad(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor, *, splits=
     Nb, H, W, Cout = dy.shape
     Cin = x.shape[-1]
     assert x.shape[:3] == dy.shape[:3] and out.numel() == Cout * 9 * Cin and out.is_contiguous()
-    if xpro is not None:
-        assert xpro.shape == (4, Cin) and xpro.is_contiguous() and variant in (0, 1)
-        fn, tail = "rk_wino4_wgrad_pro", (_p(xpro[2]), _s())
-    else:
-        fn, tail = "rk_wino4_wgrad_v", (_s(),)
+    assert xpro is None or (xpro.shape == (4, Cin) and xpro.is_contiguous() and variant in (0, 1))
     if splits == 1:
-        _lib.call(fn, _p(dy), _p(x), _p(out), Nb, H, W, Cout, Cin, 1, int(bool(accumulate)), int(variant), *tail)
-        return out
-    slab = torch.empty((splits, Cout, 9 * Cin), device=dy.device, dtype=torch.float32)
-    _lib.call(fn, _p(dy), _p(x), _p(slab), Nb, H, W, Cout, Cin, int(splits), 0, int(variant), *tail)
-    reduce_slabs(slab, out.view(Cout, 9 * Cin), accumulate=accumulate)
+        dst, acc = out, int(bool(accumulate))
+    else:
+        dst, acc = torch.empty((splits, Cout, 9 * Cin), device=dy.device, dtype=torch.float32), 0
+    _lib.call("rk_wino4_wgrad", _p(dy), _p(x), _p(dst), Nb, H, W, Cout, Cin, int(splits), acc, int(variant),
+              _pro(xpro), _s())
+    if splits != 1:
+        reduce_slabs(dst, out.view(Cout, 9 * Cin), accumulate=accumulate)
     return out
 
 
@@ -777,11 +776,7 @@ def wino4_wgrad_pt(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor, *, accu
         du = torch.empty((36, Cout, Cin), device=dy.device, dtype=torch.float32)
         m = torch.empty((36 * T, Cout), device=dy.device, dtype=torch.float32)
         v = torch.empty((36 * T, Cin), device=dy.device, dtype=torch.float32)
-        if xpro is None:
-            _lib.call("rk_wino4_pt_transform", _p(dy), _p(x), _p(m), _p(v), Nb, H, W, Cout, Cin, _s())
-        else:
-            _lib.call("rk_wino4_pt_transform_pro", _p(dy), _p(x), _p(m), _p(v), Nb, H, W, Cout, Cin, _p(xpro[2]),
-                      _s())
+        _lib.call("rk_wino4_pt_transform", _p(dy), _p(x), _p(m), _p(v), Nb, H, W, Cout, Cin, _pro(xpro), _s())
         sgemm(KIND_DENSE_DW, m, v, du, Cout, Cin, 36 * T, Cout, Cin, Cin, tile=tile, nst=nst, splits=36,
               slab_stride=Cout * Cin)
     _lib.call("rk_wino4_pt_output", _p(du), _p(out), Cout, Cin, int(bool(accumulate)), splits, 36 * Cout * Cin, _s())
@@ -923,23 +918,9 @@ def wino_conv_grp(x, u, *, out=None, bias=None, relu=False, variant=0, pool=Fals
     """k Winograd convs in one grid: x [G, Nb, H, W, C] (or [Nb, H, W, C] shared), u [G, 16, N, C],
     bias [G, N] -> out [G, Nb, H, W, N].  ``pool`` (with bias + relu, variants >= 2): the 2x2 max-pool of
     the output from the epilogue, out [G, Nb, H/2, W/2, N]."""
-    G, _, N, C = u.shape
-    shared = x.dim() == 4
-    Nb, H, W, Cx = x.shape[-4:]
-    assert Cx == C and (shared or x.shape[0] == G) and u.is_contiguous() and x.is_contiguous()
-    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
-    if out is None:
-        out = torch.empty((G, Nb, Ho, Wo, N), device=x.device, dtype=torch.float32)
-    assert out.shape == (G, Nb, Ho, Wo, N) and out.is_contiguous()
-    M = Nb * H * W
-    flags = (WF_BIAS if bias is not None else 0) | (WF_RELU if relu else 0)
-    if pool:
-        assert bias is not None and relu and variant >= 2 and H % 2 == 0 and W % 2 == 0
-        flags |= WF_POOL
-    name, v = ("rk_wino2s_conv_grp", int(variant) - 2) if variant >= 2 else ("rk_wino_conv_grp", int(variant))
-    _lib.call(name, _p(x), _p(u), _p(out), _p(bias), None, 0, None, Nb, H, W, C, N, flags,
-              v, G, 0 if shared else M * C, 16 * N * C, Nb * Ho * Wo * N, N if bias is not None else 0, _s())
-    return out
+    H, W = x.shape[-3:-1]
+    assert not pool or (bias is not None and relu and variant >= 2 and H % 2 == 0 and W % 2 == 0)
+    return _grp_conv(*_wino2_entry(variant), 16, x, u, out, bias, relu, pool)
 
 
 # ------------------------------------------------------------------------------- the route table
@@ -984,7 +965,7 @@ WINO4_PT, WINO4_PTX = -14, -15
 WINO_WGRAD, WINO4_WGRAD, WINO4_WGRAD_PT, WINO4_WGRAD_PTX = -3, -7, -13, -16
 WINO4_PTX_CFGS = tuple((WINO4_PTX, x6p_pack(t, n), s) for t, n, s in _XP_CFGS) if USE_X6P else ()
 CONV_ROUTES = {r.id: r for r in (
-    # fused F(2x2,3x3): rk_wino_conv (variants 0 / 1) and the 16x16-wave-tile kernels of winograd4.hip (2-5)
+    # fused F(2x2,3x3): rk_wino_conv_grp (variants 0 / 1) and the 16x16-wave-tile kernels of winograd4.hip (2-5)
     _fused(-1, 'F(2x2) 4-wave 64x32', 0, wino_conv, **_F2),
     _fused(-2, 'F(2x2) 8-wave 64x64', 1, wino_conv, **_F2),
     _fused(-8, 'F(2x2) 4-wave 32x32', 2, wino_conv, pool=True, **_F2),
@@ -992,7 +973,7 @@ CONV_ROUTES = {r.id: r for r in (
     _fused(-10, 'F(2x2) 8-wave 64x32', 4, wino_conv, pool=True, **_F2),
     # software-pipelined over two LDS stages: wins the 4x4-map layers
     _fused(-12, 'F(2x2) 8-wave 64x32 two-stage', 5, wino_conv, pool=True, **_F2),
-    # fused F(4x4,3x3), rk_wino4_conv.  Its software-pipelined variant 2 (4-wave 32x32 over two LDS stages, one
+    # fused F(4x4,3x3), rk_wino4_conv_grp.  Its software-pipelined variant 2 (4-wave 32x32 over two LDS stages, one
     # wave per SIMD) measured 1.3-1.5x slower than these on every VGG-small layer
     # (profiles/winograd_variants_r2e.jsonl) and has no row: it stays callable as wino4_conv(variant=2) /
     # wino4_wgrad(variant=2) for tests/test_winograd4_gpu.py

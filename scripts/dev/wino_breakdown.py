@@ -1,4 +1,4 @@
-"""Where does the fused F(4x4) forward kernel's time go?  Times rk_wino4_conv from several builds of
+"""Where does the fused F(4x4) forward kernel's time go?  Times rk_wino4_conv_grp from several builds of
 winograd4.hip compiled with experiment macros (WEXP_NOMFMA / NOLOAD / NOSTORE: skip the MFMAs, the
 global loads or the transform + LDS writes) on the VGG-small 32x32 / 16x16 shapes.
 usage: python scripts/dev/wino_breakdown.py scripts/dev/exp_so/w4_*.so > out.jsonl"""
@@ -9,7 +9,7 @@ import sys
 
 import torch
 
-vp, i32 = C.c_void_p, C.c_int
+vp, i32, i64 = C.c_void_p, C.c_int, C.c_longlong
 
 
 def t(fn, reps=30):
@@ -36,14 +36,14 @@ for (N, H, Ci, Co) in shapes:
 
 for path in sys.argv[1:]:
     lib = C.CDLL(os.path.abspath(path))
-    f = lib.rk_wino4_conv
-    f.argtypes = [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    f = lib.rk_wino4_conv_grp
+    f.argtypes = [vp, vp, vp, vp, vp, i32, vp] + [i32] * 8 + [i64] * 4 + [vp, vp]
     for key, (x, u, y, st) in bufs.items():
         N, H, Ci, Co = key
         for var in (0, 1):
             def run():
                 rc = f(x.data_ptr(), u.data_ptr(), y.data_ptr(), None, st.data_ptr(), 63, None, N, H, H, Ci, Co, 4,
-                       var, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+                       var, 1, 0, 0, 0, 0, None, C.c_void_p(torch.cuda.current_stream().cuda_stream))
                 assert rc == 0, rc
             us = t(run)
             print(json.dumps(dict(build=os.path.basename(path), N=N, H=H, Ci=Ci, Co=Co, variant=var,

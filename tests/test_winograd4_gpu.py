@@ -321,3 +321,116 @@ def test_wino4_conv_pretransformed_bn_epilogues(pool, H):
     torch.cuda.synchronize()
     assert rel(d_p, d_f) < TOL
     assert rel(acc_p.sum(0), acc_f.sum(0)) < TOL
+
+
+# ------------------------------------------------------------------------- what the launchers refuse
+# The entry points called directly, on valid tiny tensors (Nb = 1, H = W = 4, C = 8, N = 32 unless the case says
+# otherwise): every refused call returns its status (-1 RK_EBADARG, -2 RK_EUNSUPPORTED) before any launch.
+def _pro_vec(C):
+    """Identity normalise-on-load coefficients: scale [C] = 1, shift [C] = 0."""
+    return torch.cat([torch.ones(C), torch.zeros(C)]).to(DEV)
+
+
+def _fwd_call(S, name, *, H=4, C=8, N=32, flags=0, variant=0, groups=1, bias=False, stats=False, pro=False):
+    """(arguments, outputs, the other tensors behind the arguments) of rk_wino4_conv_grp / rk_wino2s_conv_grp:
+    ``groups`` convs, each with its own x, u (sized as the blocked set, the largest form), y and bias."""
+    Nb, W = 1, 4
+    x = _rand(groups, Nb, H, W, C, seed=70).abs().to(DEV)
+    u = _rand(groups, S.wino4b_numel(N, C), seed=71, scale=0.1).to(DEV)
+    y = torch.zeros(groups, Nb, H, W, N, device=DEV)
+    b = _rand(groups, N, seed=72).to(DEV) if bias else None
+    acc = torch.zeros((S.bn_slots(N), 2, N), dtype=torch.float64, device=DEV) if stats else None
+    p = _pro_vec(C) if pro else None
+    args = [S._p(x), S._p(u), S._p(y), S._p(b), S._p(acc), S._slots_flags(acc), None, Nb, H, W, C, N, flags, variant,
+            groups, x[0].numel(), u[0].numel(), y[0].numel(), N if bias else 0]
+    if name == 'rk_wino4_conv_grp':
+        args.append(S._p(p))
+    return args + [S._s()], [y], (x, u, b, acc, p)
+
+
+def _wgrad_call(S, *, splits=1, accumulate=0, variant=0, xpro=False):
+    Nb, H, W, Co, Ci = 2, 4, 4, 16, 16   # two tiles
+    dy, x = _rand(Nb, H, W, Co, seed=73).to(DEV), _rand(Nb, H, W, Ci, seed=74).abs().to(DEV)
+    out = torch.zeros(splits, Co, 9 * Ci, device=DEV)
+    p = _pro_vec(Ci) if xpro else None
+    return [S._p(dy), S._p(x), S._p(out), Nb, H, W, Co, Ci, splits, accumulate, variant, S._p(p), S._s()], \
+        [out], (dy, x, p)
+
+
+def _pt_transform_call(S, *, Co=8, Ci=8, xpro=False):
+    dy, x = _rand(1, 4, 4, Co, seed=75).to(DEV), _rand(1, 4, 4, Ci, seed=76).abs().to(DEV)
+    m, v = torch.zeros(36, 1, Co, device=DEV), torch.zeros(36, 1, Ci, device=DEV)
+    p = _pro_vec(Ci) if xpro else None
+    return [S._p(dy), S._p(x), S._p(m), S._p(v), 1, 4, 4, Co, Ci, S._p(p), S._s()], [m, v], (dy, x, p)
+
+
+def _pt_input_call(S, *, C=8, planes=False, pro=False):
+    """rk_wino4_pt_input (v [36][T][C] fp32) / rk_x6p_w4_input (``planes``: v [36][3][T][C] bf16), T = 1."""
+    x = _rand(1, 4, 4, C, seed=77).abs().to(DEV)
+    v = torch.zeros(36, 3, 1, C, dtype=torch.bfloat16, device=DEV) if planes else torch.zeros(36, 1, C, device=DEV)
+    p = _pro_vec(C) if pro else None
+    return [S._p(x), S._p(v), 1, 4, 4, C, S._p(p), S._s()], [v], (x, p)
+
+
+_W4, _W2S = 'rk_wino4_conv_grp', 'rk_wino2s_conv_grp'
+_REFUSALS = {
+    'conv4 H = 6': (-1, lambda S: (_W4, _fwd_call(S, _W4, H=6))),
+    'conv4 WF_STATS, null stats': (-1, lambda S: (_W4, _fwd_call(S, _W4, flags=S.WF_STATS))),
+    'conv4 WF_BIAS, null bias': (-1, lambda S: (_W4, _fwd_call(S, _W4, flags=S.WF_BIAS))),
+    'conv4 groups = 2, WF_STATS': (-2, lambda S: (_W4, _fwd_call(S, _W4, groups=2, flags=S.WF_STATS, stats=True))),
+    'conv4 variant 6': (-1, lambda S: (_W4, _fwd_call(S, _W4, variant=6))),
+    'conv4 WF_POOL alone': (-2, lambda S: (_W4, _fwd_call(S, _W4, flags=S.WF_POOL))),
+    'conv4 pro, variant 0': (-2, lambda S: (_W4, _fwd_call(S, _W4, pro=True))),
+    'conv4 pro, bias + relu': (-2, lambda S: (_W4, _fwd_call(S, _W4, pro=True, variant=3, bias=True,
+                                                             flags=S.WF_BIAS | S.WF_RELU))),
+    'conv4 pro, C = 520': (-2, lambda S: (_W4, _fwd_call(S, _W4, pro=True, variant=3, C=520))),
+    'conv4 pro, groups = 2': (-2, lambda S: (_W4, _fwd_call(S, _W4, pro=True, variant=3, groups=2))),
+    'conv2s variant 4': (-1, lambda S: (_W2S, _fwd_call(S, _W2S, variant=4))),
+    'wgrad splits = 2, accumulate': (-1, lambda S: ('rk_wino4_wgrad', _wgrad_call(S, splits=2, accumulate=1))),
+    # 2 tiles in chunks of 8 per split: one split holds both, the second is empty
+    'wgrad empty split': (-1, lambda S: ('rk_wino4_wgrad', _wgrad_call(S, splits=2))),
+    'wgrad xpro, variant 2': (-2, lambda S: ('rk_wino4_wgrad', _wgrad_call(S, variant=2, xpro=True))),
+    'pt_transform Co = 6': (-2, lambda S: ('rk_wino4_pt_transform', _pt_transform_call(S, Co=6))),
+    'pt_input C = 6': (-2, lambda S: ('rk_wino4_pt_input', _pt_input_call(S, C=6))),
+    'x6p_w4_input C = 6': (-2, lambda S: ('rk_x6p_w4_input', _pt_input_call(S, C=6, planes=True))),
+}
+
+
+@pytest.mark.parametrize("case", list(_REFUSALS))
+def test_wino4_launchers_refuse(case):
+    from rafiki_amd.ops import _lib
+    from rafiki_amd.ops import f32 as S
+    status, build = _REFUSALS[case]
+    name, (args, _outs, _keep) = build(S)
+    with pytest.raises(_lib.KernelError, match=r'{} failed with status {}$'.format(name, status)):
+        _lib.call(name, *args)
+
+
+_ACCEPTS = {
+    'rk_wino4_conv_grp': lambda S, pro: _fwd_call(S, _W4, variant=3, pro=pro),
+    'rk_wino4_wgrad': lambda S, pro: _wgrad_call(S, xpro=pro),
+    'rk_wino4_pt_transform': lambda S, pro: _pt_transform_call(S, xpro=pro),
+    'rk_wino4_pt_input': lambda S, pro: _pt_input_call(S, pro=pro),
+    'rk_x6p_w4_input': lambda S, pro: _pt_input_call(S, planes=True, pro=pro),
+}
+
+
+@pytest.mark.parametrize("name", list(_ACCEPTS))
+def test_wino4_merged_entry_points_take_pro_or_null(name):
+    """Each merged entry point runs with pro = NULL and with pro given.  x >= 0 and pro is the identity (scale 1,
+    shift 0), so relu(x * 1 + 0) == x exactly and both calls compute the same thing: the transforms (one
+    kernel, pro a run-time pointer) to the bit, the conv and the weight gradient within this file's gate."""
+    from rafiki_amd.ops import _lib
+    from rafiki_amd.ops import f32 as S
+    outs = []
+    for pro in (False, True):
+        args, written, _keep = _ACCEPTS[name](S, pro)
+        _lib.call(name, *args)
+        torch.cuda.synchronize()
+        outs.append([t.float() for t in written])
+    for a, b in zip(*outs):
+        assert b.abs().sum().item() > 0
+        if name in ('rk_wino4_conv_grp', 'rk_wino4_wgrad'):
+            assert rel(a, b) < TOL
+        else:
+            assert torch.equal(a, b)
