@@ -10,6 +10,7 @@
 //  * rk_lerp (Gs EMA, pg_gans.py:730-740), rk_nonfinite_count (pg_gans.py:1180-1191),
 //    rk_reduce_slabs (split-K combine), rk_colsum (bias grads), rk_ensemble_mean (predictor).
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -314,6 +315,27 @@ __global__ __launch_bounds__(256) void reduce_slabs_epi_kernel(const float* __re
 // zero the step's fp64 BatchNorm slot tables (`zero`, zero_n doubles) and, with `done`, advance the
 // device step counter once every block has read it (the last block to arrive bumps it) — replaces a
 // memset node and a separate counter-increment kernel (~4 us of dispatch each).
+//
+// AUG = true (rk_gather_batch_aug) is the same prologue with pad-and-crop plus mirror augmentation folded
+// into the copy: a row is an NHWC image of H x W pixels of vpp 16-B vectors, and sample b, read from row
+// src, draws one Philox block keyed (seed; src, stream_id, *epoch) -> a shift (dy, dx) in [-pad, pad]^2 and
+// a mirror flag, then out[b, y, x] = data[src, y + dy, (flip ? W-1-x : x) + dx] or a zero vector outside
+// the image.  The draw depends on the image and the epoch alone, not on the batch position or the step, so
+// replays, a resumed trial and the host twin (rafiki_amd/ops/augment.py) see the same images.  Only the
+// address of each vector changes; lanes still read consecutive vectors of a line (backwards when mirrored).
+template <bool AUG> struct GatherAug {};
+template <> struct GatherAug<true> {
+  int H, W, vpp, pad;
+  float flip_p;
+  uint32_t k0, k1, stream_id;
+  const int* epoch;  // device int32, null: epoch 0
+};
+struct AugDraw {
+  long long src;
+  int dy, dx, flip;
+};
+
+template <bool AUG>
 __global__ __launch_bounds__(256) void gather_batch_kernel(const uint4* __restrict__ data, long long row_vec,
                                                            const int* __restrict__ labels,
                                                            const long long* __restrict__ sched,
@@ -321,7 +343,8 @@ __global__ __launch_bounds__(256) void gather_batch_kernel(const uint4* __restri
                                                            uint4* __restrict__ out, int* __restrict__ out_y,
                                                            double* __restrict__ zero, long long zero_n,
                                                            int* __restrict__ done, const float* __restrict__ lr_table,
-                                                           float* __restrict__ lr_out, int nsteps, long long nrows) {
+                                                           float* __restrict__ lr_out, int nsteps, long long nrows,
+                                                           const GatherAug<AUG> aug) {
   // the schedule holds nsteps rows: a counter past it wraps around (warm-up runs, extra replays) instead
   // of reading beyond the buffers; row indices outside the dataset read row 0
   const long long step = (long long)((unsigned)*counter % (unsigned)nsteps);
@@ -329,13 +352,55 @@ __global__ __launch_bounds__(256) void gather_batch_kernel(const uint4* __restri
   if (lr_table && blockIdx.x == 0 && threadIdx.x == 0) *lr_out = lr_table[step];
   const long long total = (long long)B * row_vec;
   const long long gstride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gstride) {
-    const int b = (int)(i / row_vec);
-    const long long c = i - (long long)b * row_vec;
-    long long src = sched[step * B + b];
-    if ((unsigned long long)src >= (unsigned long long)nrows) src = 0;
-    out[i] = data[src * row_vec + c];
-    if (c == 0 && out_y) out_y[b] = labels[src];
+  if constexpr (AUG) {
+    // The 10 Philox rounds run once per (block, sample), not once per vector: a block's 256 consecutive
+    // vectors start in sample b0 and touch at most 256 samples, thread t draws for sample b0 + t and every
+    // thread then picks its sample's draw out of LDS.  The trip count is the same for a whole block.
+    __shared__ AugDraw draws[256];
+    const uint32_t ep = aug.epoch ? (uint32_t)*aug.epoch : 0u;
+    const unsigned line_vec = (unsigned)(aug.W * aug.vpp);
+    const int span = 2 * aug.pad + 1;
+    for (long long base = (long long)blockIdx.x * blockDim.x; base < total; base += gstride) {
+      const int b0 = (int)(base / row_vec);
+      const int bt = b0 + (int)threadIdx.x;
+      if (bt < B && (long long)bt * row_vec < base + blockDim.x) {
+        long long src = sched[step * B + bt];
+        if ((unsigned long long)src >= (unsigned long long)nrows) src = 0;
+        const U4 r = philox4x32_10((uint32_t)src, (uint32_t)(src >> 32), aug.stream_id, ep, aug.k0, aug.k1);
+        const int ry = (int)(u01(r.v[0]) * (float)span), rx = (int)(u01(r.v[1]) * (float)span);
+        AugDraw d;
+        d.src = src;
+        d.dy = (ry < span ? ry : span - 1) - aug.pad;
+        d.dx = (rx < span ? rx : span - 1) - aug.pad;
+        d.flip = u01(r.v[2]) < aug.flip_p;
+        draws[threadIdx.x] = d;
+      }
+      __syncthreads();
+      const long long i = base + threadIdx.x;
+      if (i < total) {
+        const int b = (int)(i / row_vec);
+        const unsigned c = (unsigned)(i - (long long)b * row_vec);
+        const AugDraw d = draws[b - b0];
+        const unsigned y = c / line_vec, cl = c - y * line_vec;
+        const unsigned x = cl / (unsigned)aug.vpp, v = cl - x * (unsigned)aug.vpp;
+        const int sy = (int)y + d.dy, sx = (d.flip ? aug.W - 1 - (int)x : (int)x) + d.dx;
+        uint4 val = {0u, 0u, 0u, 0u};  // the border: zero is mid-grey after x / 127.5 - 1, bf16 and fp32 alike
+        if ((unsigned)sy < (unsigned)aug.H && (unsigned)sx < (unsigned)aug.W)
+          val = data[d.src * row_vec + ((long long)sy * aug.W + sx) * aug.vpp + v];
+        out[i] = val;
+        if (c == 0 && out_y) out_y[b] = labels[d.src];
+      }
+      __syncthreads();  // every thread has its draw before the next trip overwrites the table
+    }
+  } else {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gstride) {
+      const int b = (int)(i / row_vec);
+      const long long c = i - (long long)b * row_vec;
+      long long src = sched[step * B + b];
+      if ((unsigned long long)src >= (unsigned long long)nrows) src = 0;
+      out[i] = data[src * row_vec + c];
+      if (c == 0 && out_y) out_y[b] = labels[src];
+    }
   }
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < zero_n; i += gstride) zero[i] = 0.0;
   if (done) {
@@ -782,9 +847,34 @@ extern "C" int rk_gather_batch(const void* data, long long row_bytes, const int*
   if (row_bytes % 16 || zero_n < 0 || (zero_n && !zero) || (lr_table && !lr_out)) return RK_EUNSUPPORTED;
   if (nsteps <= 0 || nrows <= 0) return RK_EBADARG;
   const long long rv = row_bytes / 16;
-  hipLaunchKernelGGL(gather_batch_kernel, dim3(grid_for((long long)B * rv, 2048)), dim3(256), 0, (hipStream_t)stream,
-                     (const uint4*)data, rv, labels, sched, counter, B, (uint4*)out, out_y, zero, zero_n, done,
-                     lr_table, lr_out, nsteps, nrows);
+  hipLaunchKernelGGL(gather_batch_kernel<false>, dim3(grid_for((long long)B * rv, 2048)), dim3(256), 0,
+                     (hipStream_t)stream, (const uint4*)data, rv, labels, sched, counter, B, (uint4*)out, out_y, zero,
+                     zero_n, done, lr_table, lr_out, nsteps, nrows, GatherAug<false>{});
+  RK_LAUNCH_CHECK();
+  return RK_OK;
+}
+
+// rk_gather_batch with the augmentation of gather_batch_kernel<true>: a row is H x W pixels of vpp 16-B
+// vectors (1: bf16 C=8 or fp32 C=4, 2: fp32 C=8), shifts are uniform in [-pad, pad], the mirror has
+// probability flip_p; epoch: device int32 (null: 0), the fourth Philox counter word
+extern "C" int rk_gather_batch_aug(const void* data, long long row_bytes, const int* labels, const long long* sched,
+                                   int* counter, int B, void* out, int* out_y, double* zero, long long zero_n,
+                                   int* done, const float* lr_table, float* lr_out, int nsteps, long long nrows,
+                                   int H, int W, int vpp, int pad, float flip_p, unsigned long long seed,
+                                   unsigned int stream_id, const int* epoch, void* stream) {
+  if (zero_n < 0 || (zero_n && !zero) || (lr_table && !lr_out)) return RK_EUNSUPPORTED;
+  // extents small enough that the product below cannot overflow, rows small enough for 32-bit vector indices
+  if (H <= 0 || W <= 0 || vpp <= 0 || H > 65535 || W > 65535 || vpp > 4096) return RK_EUNSUPPORTED;
+  if (row_bytes > 16LL * 0x7fffffff || row_bytes != 16LL * H * W * vpp) return RK_EUNSUPPORTED;
+  if (pad < 0 || pad >= (H < W ? H : W) || !(flip_p >= 0.f && flip_p <= 1.f)) return RK_EUNSUPPORTED;
+  if (nsteps <= 0 || nrows <= 0) return RK_EBADARG;
+  const long long rv = row_bytes / 16;
+  GatherAug<true> aug;
+  aug.H = H, aug.W = W, aug.vpp = vpp, aug.pad = pad, aug.flip_p = flip_p;
+  aug.k0 = (uint32_t)seed, aug.k1 = (uint32_t)(seed >> 32), aug.stream_id = (uint32_t)stream_id, aug.epoch = epoch;
+  hipLaunchKernelGGL(gather_batch_kernel<true>, dim3(grid_for((long long)B * rv, 2048)), dim3(256), 0,
+                     (hipStream_t)stream, (const uint4*)data, rv, labels, sched, counter, B, (uint4*)out, out_y, zero,
+                     zero_n, done, lr_table, lr_out, nsteps, nrows, aug);
   RK_LAUNCH_CHECK();
   return RK_OK;
 }

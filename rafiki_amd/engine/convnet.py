@@ -121,7 +121,8 @@ class ConvNetEngine:
                  cfg: Sequence = VGG_SMALL_CFG, fc_dims: Sequence[int] = (512,), device='cuda', seed: int = 0,
                  bn_eps: float = 1e-5, bn_momentum: float = 0.1, optimizer: str = 'sgd', lr: float = 0.05,
                  momentum: float = 0.9, weight_decay: float = 5e-4, nesterov: bool = True,
-                 betas=(0.9, 0.999), input_bn: bool = False, dtype: Optional[str] = None, bn: bool = True):
+                 betas=(0.9, 0.999), input_bn: bool = False, dtype: Optional[str] = None, bn: bool = True,
+                 augment: Optional[dict] = None):
         self.device = torch.device(device)
         self.dtype = dtype or default_dtype()
         if self.dtype not in DTYPES:
@@ -143,6 +144,20 @@ class ConvNetEngine:
         self.input_bn = bool(input_bn)
         if self.input_bn and not self.flat_input:
             raise ValueError('input_bn is for fully-connected nets (no conv blocks)')
+        # augment {'pad': int, 'flip': float}: training batches are shifted by up to pad pixels each way (zero
+        # border) and mirrored with probability flip, drawn per (seed, epoch, image) — in the scheduled graph's
+        # prologue launch (capture_scheduled) or by augment_batch; None: every batch is the stored images
+        self.augment = None
+        if augment is not None:
+            if self.flat_input:
+                raise ValueError('augment needs image inputs (conv blocks), not a flat-input net')
+            pad, flip = int(augment.get('pad', 0)), float(augment.get('flip', 0.0))
+            if set(augment) - {'pad', 'flip'} or not 0 <= pad < image_size or not 0.0 <= flip <= 1.0:
+                raise ValueError("augment must be {{'pad': 0..{}, 'flip': 0..1}}, got {!r}".format(
+                    image_size - 1, augment))
+            self.augment = {'pad': pad, 'flip': flip}
+        self._aug_seed = int(seed)
+        self._aug_epoch = self._aug_ctr0 = None
         # any image size: power-of-two maps use the shift-decoded (and LDS-DMA) gather, others the
         # reciprocal-decoded register-staged gather (VGG16 at 48x48: 48/24/12/6/3)
         flat = FlatParams(self.device, seed, compute_bf16=not self.f32)
@@ -719,12 +734,16 @@ class ConvNetEngine:
         # the prologue once every gather block has read it
         opt_bumps = isinstance(self.opt, FlatSGD)
 
+        gather, aug = F.gather_batch, {}
+        if self.augment is not None:
+            gather, aug = F.gather_batch_aug, self._aug_args()
+
         def body():
-            # one prologue launch: gather + zero the BN slot tables (+ counter)
-            F.gather_batch(self._data, self._labels, self._sched, self._ctr, self._static_x, self._static_y,
-                           zero=self._bn_acc_flat if accs is not None else None,
-                           done=None if opt_bumps else self._done,
-                           lr_table=self._lr_table if lr_out is not None else None, lr_out=lr_out)
+            # one prologue launch: gather (+ augment) + zero the BN slot tables (+ counter)
+            gather(self._data, self._labels, self._sched, self._ctr, self._static_x, self._static_y,
+                   zero=self._bn_acc_flat if accs is not None else None,
+                   done=None if opt_bumps else self._done,
+                   lr_table=self._lr_table if lr_out is not None else None, lr_out=lr_out, **aug)
             self._acc_zeroed_by_prologue = accs is not None
             if opt_bumps:
                 self.opt.bump = self._ctr
@@ -757,16 +776,44 @@ class ConvNetEngine:
         self._sched_graph = g
         return g
 
-    def set_schedule(self, idx, start: int = 0, lr_scales=None):
+    def set_schedule(self, idx, start: int = 0, lr_scales=None, epoch=None):
         """idx: [steps, B] row indices (device) -> schedule buffer; the next replay uses row ``start``.
-        ``lr_scales`` [steps] (optional): the optimizer's LR multiplier of each step."""
+        ``lr_scales`` [steps] (optional): the optimizer's LR multiplier of each step.  ``epoch`` (optional, an
+        augmenting engine): the epoch the replays draw their crops and mirrors for."""
         self._sched[:idx.shape[0]].copy_(idx)
         self._ctr.fill_(start)
         if lr_scales is not None:
             self._lr_table[:len(lr_scales)].copy_(torch.as_tensor(lr_scales, dtype=torch.float32))
+        if epoch is not None and self.augment is not None:
+            self._aug_epoch.fill_(int(epoch))
 
     def replay(self):
         self._sched_graph.replay()
+
+    def _aug_args(self):
+        """The augmentation arguments of F.gather_batch_aug; the device epoch word is made on first use."""
+        from ..ops.augment import AUG_STREAM
+        if self._aug_epoch is None:
+            self._aug_epoch = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self._aug_ctr0 = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return dict(pad=self.augment['pad'], flip_p=self.augment['flip'], seed=self._aug_seed,
+                    stream_id=AUG_STREAM, epoch=self._aug_epoch)
+
+    def augment_batch(self, data, idx, epoch, out_x):
+        """out_x[b] = the augmented image data[idx[b]] of ``epoch`` — what the scheduled graph's prologue gives
+        for the same (idx, epoch): on the GPU the same kernel over a one-row schedule, on the CPU its host
+        twin.  For the loops that feed the step themselves (``step_graph`` / ``train_step``)."""
+        if self.augment is None:
+            raise RuntimeError('augment_batch on an engine built without augment')
+        if self.device.type == 'cuda':
+            args = self._aug_args()
+            self._aug_epoch.fill_(int(epoch))
+            return F.gather_batch_aug(data, None, idx.reshape(1, -1), self._aug_ctr0, out_x, None, **args)
+        from ..ops import augment as A
+        idx = torch.as_tensor(idx, dtype=torch.int64).reshape(-1)
+        idx = torch.where((idx < 0) | (idx >= data.shape[0]), torch.zeros_like(idx), idx)
+        dy, dx, flip = A.draws(self._aug_seed, idx, epoch, self.augment['pad'], self.augment['flip'])
+        return out_x.copy_(A.apply(data, idx, dy, dx, flip))
 
     def _opt_tensors(self):
         o = self.opt

@@ -1,6 +1,7 @@
 """Model zoo: single-file BaseModel classes uploadable through the client.
 
   VggSmall (vgg_small.py)        gfx950 engine, the BASELINE benchmark architecture
+  VggSmallAug (vgg_small.py)     VggSmall with the crop / mirror augmentation in the search space
   Vgg16 (vgg16.py)               gfx950 engine, TfVgg16 semantics (48x48x3, Adam)
   FeedForward (feed_forward.py)  gfx950 engine, TfFeedForward semantics
   SkDt, SkSvm (sk_models.py)     scikit-learn on CPU
@@ -12,6 +13,7 @@ import os
 MODELS_DIR = os.path.dirname(os.path.abspath(__file__))
 ZOO = {
     'VggSmall': ('vgg_small.py', 'IMAGE_CLASSIFICATION'),
+    'VggSmallAug': ('vgg_small.py', 'IMAGE_CLASSIFICATION'),
     'VggSmallTrial': ('vgg_small.py', 'IMAGE_CLASSIFICATION'),
     'VggSmallProbe': ('vgg_small.py', 'IMAGE_CLASSIFICATION'),
     'Vgg16': ('vgg16.py', 'IMAGE_CLASSIFICATION'),

@@ -53,8 +53,24 @@ class NativeImageClassifier(BaseModel):
             images = dataset_utils.resize_as_images(images, self.image_size)
         return images, labels, ds.classes
 
-    def _build(self, num_classes, channels, dtype=None):
+    AUGMENT_MODES = ('none', 'flip', 'crop', 'crop_flip')
+
+    def _augment(self):
+        """The engine's ``augment`` argument from the knobs ``augment`` (one of AUGMENT_MODES, default 'none':
+        mirror with probability 0.5, pad-and-crop by up to ``augment_pad`` pixels, or both) and ``augment_pad``
+        (default 4, kept below the image size).  Training only: evaluation and prediction never augment."""
+        mode = self._knobs.get('augment', 'none')
+        if mode not in self.AUGMENT_MODES:
+            raise ValueError('augment must be one of {}, got {!r}'.format(self.AUGMENT_MODES, mode))
+        if mode == 'none':
+            return None
+        pad = max(0, min(int(self._knobs.get('augment_pad', 4)), self.image_size - 1))
+        return {'pad': pad if 'crop' in mode else 0, 'flip': 0.5 if 'flip' in mode else 0.0}
+
+    def _build(self, num_classes, channels, dtype=None, augment=None):
         kw = self._engine_kwargs(num_classes, channels, self.image_size)
+        if augment is not None:
+            kw['augment'] = augment
         # compute dtype: fp32 (reference precision) unless the trial / RAFIKI_DTYPE opts into bf16
         kw.setdefault('dtype', dtype or self._knobs.get('dtype') or default_dtype())
         self._engine = ConvNetEngine(num_classes=num_classes, in_channels=channels, image_size=self.image_size,
@@ -66,10 +82,11 @@ class NativeImageClassifier(BaseModel):
     def train(self, dataset_uri):
         tm = self.timings = {}
         t_start = time.perf_counter()
+        augment = self._augment()
         images, labels, classes = self._load(dataset_uri)
         tm['load'] = time.perf_counter() - t_start
         channels = 1 if images.ndim == 3 else images.shape[-1]
-        self._build(max(classes, 2), channels)
+        self._build(max(classes, 2), channels, augment=augment)
         tm['build'] = time.perf_counter() - t_start - tm['load']
         eng = self._engine
         x_all = eng.prepare_inputs(images)
@@ -118,7 +135,8 @@ class NativeImageClassifier(BaseModel):
                 cosine = hasattr(eng.opt, 'set_lr_scale') and sched == 'cosine'
                 lrs = [0.5 * (1.0 + math.cos(math.pi * (step + b) / total)) if cosine else 1.0
                        for b in range(steps_per_epoch)]
-                eng.set_schedule(perm[:steps_per_epoch * bs].view(steps_per_epoch, bs), lr_scales=lrs)
+                # the crops and mirrors are drawn per (seed, epoch, image): a resumed trial continues the stream
+                eng.set_schedule(perm[:steps_per_epoch * bs].view(steps_per_epoch, bs), lr_scales=lrs, epoch=epoch)
             for b in range(steps_per_epoch):
                 if step >= total:
                     break
@@ -131,7 +149,10 @@ class NativeImageClassifier(BaseModel):
                 if hasattr(eng.opt, 'set_lr_scale') and sched == 'cosine':
                     eng.opt.set_lr_scale(0.5 * (1.0 + math.cos(math.pi * step / total)))
                 idx = perm[b * bs:(b + 1) * bs]
-                torch.index_select(x_all, 0, idx, out=xb)
+                if augment is not None:
+                    eng.augment_batch(x_all, idx, epoch, xb)
+                else:
+                    torch.index_select(x_all, 0, idx, out=xb)
                 torch.index_select(y_all, 0, idx, out=yb)
                 if use_graph:
                     eng.step_graph(xb, yb)

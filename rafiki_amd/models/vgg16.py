@@ -30,6 +30,7 @@ class Vgg16(NativeImageClassifier):
             'learning_rate': FloatKnob(1e-5, 1e-2, is_exp=True),
             'batch_size': CategoricalKnob([16, 32, 64, 128]),
             'batch_norm': FixedKnob(False),
+            'augment': FixedKnob('none'),
         }
 
     def _load(self, uri):

@@ -24,6 +24,7 @@ class VggSmall(NativeImageClassifier):
             'batch_size': CategoricalKnob([64, 128, 256]),
             'width_mult': CategoricalKnob([0.5, 1.0]),
             'image_size': FixedKnob(32),
+            'augment': FixedKnob('none'),
         }
 
     def _engine_kwargs(self, num_classes, channels, image_size):
@@ -33,6 +34,18 @@ class VggSmall(NativeImageClassifier):
         return dict(cfg=cfg, fc_dims=(max(64, int(512 * wm)),), optimizer='sgd',
                     lr=float(k.get('learning_rate', 0.05)), momentum=float(k.get('momentum', 0.9)),
                     weight_decay=float(k.get('weight_decay', 5e-4)), nesterov=True)
+
+
+class VggSmallAug(VggSmall):
+    """VggSmall with the training augmentation in the search space: none, mirroring, or pad-and-crop by up to
+    ``augment_pad`` (default 4) pixels plus mirroring — drawn per (seed, epoch, image) inside the step graph's
+    prologue launch (``ConvNetEngine(augment=...)``)."""
+
+    @staticmethod
+    def get_knob_config():
+        cfg = VggSmall.get_knob_config()
+        cfg['augment'] = CategoricalKnob(['none', 'flip', 'crop_flip'])
+        return cfg
 
 
 class VggSmallTrial(VggSmall):

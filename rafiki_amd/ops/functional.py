@@ -896,6 +896,34 @@ def gather_batch(data, labels, sched, counter, out_x, out_y, *, zero=None, done=
     return out_x
 
 
+def gather_batch_aug(data, labels, sched, counter, out_x, out_y, *, pad, flip_p, seed, stream_id, epoch=None,
+                     zero=None, done=None, lr_table=None, lr_out=None):
+    """``gather_batch`` with random-crop and mirror augmentation folded into the copy (same launch, same
+    prologue duties).  ``data`` [N, H, W, C] NHWC with 16 * vpp bytes per pixel; sample b, read from row src,
+    is shifted by (dy, dx) uniform in [-pad, pad]^2 (zero border) and mirrored with probability ``flip_p``,
+    drawn from Philox (seed; src, stream_id, *epoch) — ``epoch`` a device int32 [1] (None: 0).
+    ``rafiki_amd.ops.augment`` is the host twin of the draws and of the copy."""
+    B = out_x.shape[0]
+    if data.dim() != 4:
+        raise ValueError('gather_batch_aug: data must be NHWC [N, H, W, C], got {}'.format(tuple(data.shape)))
+    H, W = int(data.shape[1]), int(data.shape[2])
+    row_bytes = data[0].numel() * data.element_size()
+    pixel_bytes = data.shape[3] * data.element_size()   # not a multiple of 16: the kernel refuses the row size
+    if zero is not None:
+        assert zero.dtype == torch.float64 and zero.is_contiguous()
+    if sched.dim() != 2 or sched.shape[1] != B or sched.dtype != torch.int64:
+        raise ValueError('sched must be int64 [steps, {}], got {} {}'.format(B, sched.dtype, tuple(sched.shape)))
+    if lr_table is not None and lr_table.numel() < sched.shape[0]:
+        raise ValueError('lr_table shorter than the schedule')
+    if epoch is not None and (epoch.dtype != torch.int32 or epoch.device != data.device):
+        raise ValueError('epoch must be a device int32 tensor')
+    _lib.call("rk_gather_batch_aug", _p(data), row_bytes, _p(labels), _p(sched), _p(counter), B, _p(out_x), _p(out_y),
+              _p(zero), 0 if zero is None else zero.numel(), _p(done), _p(lr_table), _p(lr_out), sched.shape[0],
+              data.shape[0], H, W, pixel_bytes // 16, int(pad), float(flip_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+              int(stream_id) & 0xFFFFFFFF, _p(epoch), _s())
+    return out_x
+
+
 def cast_bf16(src, dst):
     _lib.call("rk_cast_f32_bf16", _p(src), _p(dst), src.numel(), _s())
     return dst
