@@ -8,6 +8,8 @@
 //
 //   head_fwd_bwd (one wave per row b):  logits = z W^T + bias; log-softmax; loss / #correct;
 //     dlogits = (softmax - onehot(y)) * grad_scale over the ncls real classes (0 in the padding);
+//     SOFT (rk_head_fwd_bwd_soft): softmax - t with the soft target t_c = (1 - eps) * (lam [c == ya] +
+//     (1 - lam) [c == yb]) + eps / ncls (label smoothing, mixup, CutMix; lam a device scalar of the step);
 //     dz = (dlogits W) gated by z > 0 (the hidden layer's ReLU; ungated without a gate)
 //   head_dw (one block per 8 columns k):  dW[c][k] = sum_b dlogits[b][c] z[b][k], db[c] = sum_b dlogits[b][c]
 //     and, for the hidden layer, dbh[k] = sum_b dz[b][k] (its bias gradient)
@@ -16,13 +18,21 @@
 
 namespace {
 
-template <int NC>
+// The soft target's extra arguments: labels2 (nullable: smoothing only), lam (device, nullable: 1), eps.
+template <bool SOFT> struct HeadSoft {};
+template <> struct HeadSoft<true> {
+  const int* labels2;
+  const float* lam;
+  float eps;
+};
+
+template <int NC, bool SOFT>
 __global__ __launch_bounds__(256) void head_fwd_bwd_kernel(const float* __restrict__ z, int D,
                                                            const float* __restrict__ w, const float* __restrict__ bias,
                                                            const int* __restrict__ labels, int B, int ncls,
                                                            float grad_scale, float* __restrict__ dlogits,
                                                            float* __restrict__ dz, int gated, float* loss_sum,
-                                                           int* correct, int* counted) {
+                                                           int* correct, int* counted, const HeadSoft<SOFT> soft) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= B) return;
@@ -53,11 +63,29 @@ __global__ __launch_bounds__(256) void head_fwd_bwd_kernel(const float* __restri
     if (c < ncls) se += __expf(logit[c] - mx);
   const float lse = mx + __logf(se);
   const int y = labels[row];
-  const bool valid = y >= 0 && y < ncls;
+  bool valid = y >= 0 && y < ncls;
   float g[NC];
+  // SOFT: the partner label and the two labels' shares (wa + wb = 1 up to rounding; 1 and 0 without a partner)
+  int y2 = y;
+  float wa = 1.f, wb = 0.f;
+  if constexpr (SOFT) {
+    if (soft.labels2) {
+      y2 = soft.labels2[row];
+      valid = valid && y2 >= 0 && y2 < ncls;
+      wa = soft.lam ? soft.lam[0] : 1.f;
+      wb = 1.f - wa;
+    }
+    const float ome = 1.f - soft.eps, tu = soft.eps / (float)ncls;
 #pragma unroll
-  for (int c = 0; c < NC; ++c)
-    g[c] = (valid && c < ncls) ? (__expf(logit[c] - lse) - (c == y ? 1.f : 0.f)) * grad_scale : 0.f;
+    for (int c = 0; c < NC; ++c) {
+      const float t = ome * (wa * (c == y ? 1.f : 0.f) + wb * (c == y2 ? 1.f : 0.f)) + tu;
+      g[c] = (valid && c < ncls) ? (__expf(logit[c] - lse) - t) * grad_scale : 0.f;
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+      g[c] = (valid && c < ncls) ? (__expf(logit[c] - lse) - (c == y ? 1.f : 0.f)) * grad_scale : 0.f;
+  }
   if (lane < NC) {
     float v = 0.f;
 #pragma unroll
@@ -68,8 +96,21 @@ __global__ __launch_bounds__(256) void head_fwd_bwd_kernel(const float* __restri
     float ly = 0.f;
 #pragma unroll
     for (int c = 0; c < NC; ++c) ly = c == y ? logit[c] : ly;
-    if (loss_sum) atomicAdd(loss_sum, lse - ly);
-    if (correct) atomicAdd(correct, amax == y ? 1 : 0);
+    if constexpr (SOFT) {
+      // loss = lse - (1 - eps) (wa l_ya + wb l_yb) - eps / ncls * sum_c l_c, the sum in class order
+      float ly2 = 0.f, ls = 0.f;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        ly2 = c == y2 ? logit[c] : ly2;
+        ls += c < ncls ? logit[c] : 0.f;
+      }
+      if (loss_sum)
+        atomicAdd(loss_sum, lse - (1.f - soft.eps) * (wa * ly + wb * ly2) - soft.eps / (float)ncls * ls);
+      if (correct) atomicAdd(correct, amax == (wa >= 0.5f ? y : y2) ? 1 : 0);
+    } else {
+      if (loss_sum) atomicAdd(loss_sum, lse - ly);
+      if (correct) atomicAdd(correct, amax == y ? 1 : 0);
+    }
     if (counted) atomicAdd(counted, 1);
   }
   // dz = dlogits . W, gated by the hidden layer's ReLU output
@@ -146,23 +187,45 @@ __global__ __launch_bounds__(256) void head_dw_kernel(const float* __restrict__ 
 
 // z [B][D] (D % 4 == 0), w [NC][D], bias [NC] (nullable), labels [B] int32 -> dlogits [B][NC], dz [B][D]
 // (gated by z > 0 when `gated`); loss / correct / counted accumulate (nullable).  NC in {8, 16, 32}.
-extern "C" int rk_head_fwd_bwd(const float* z, int B, int D, const float* w, const float* bias, int NC,
+template <bool SOFT>
+static int head_fwd_bwd_launch(const float* z, int B, int D, const float* w, const float* bias, int NC,
                                const int* labels, int ncls, float grad_scale, float* dlogits, float* dz, int gated,
-                               float* loss_sum, int* correct, int* counted, void* stream) {
+                               float* loss_sum, int* correct, int* counted, const HeadSoft<SOFT> soft, void* stream) {
   if (B <= 0 || D <= 0 || (D & 3) || ncls <= 0 || ncls > NC || !labels || !dlogits || !dz) return RK_EBADARG;
   const dim3 grid(rk_cdiv(B, 4)), block(256);
   const hipStream_t st = (hipStream_t)stream;
   switch (NC) {
-    case 8: hipLaunchKernelGGL(head_fwd_bwd_kernel<8>, grid, block, 0, st, z, D, w, bias, labels, B, ncls, grad_scale,
-                               dlogits, dz, gated, loss_sum, correct, counted); break;
-    case 16: hipLaunchKernelGGL(head_fwd_bwd_kernel<16>, grid, block, 0, st, z, D, w, bias, labels, B, ncls,
-                                grad_scale, dlogits, dz, gated, loss_sum, correct, counted); break;
-    case 32: hipLaunchKernelGGL(head_fwd_bwd_kernel<32>, grid, block, 0, st, z, D, w, bias, labels, B, ncls,
-                                grad_scale, dlogits, dz, gated, loss_sum, correct, counted); break;
+    case 8: hipLaunchKernelGGL((head_fwd_bwd_kernel<8, SOFT>), grid, block, 0, st, z, D, w, bias, labels, B, ncls,
+                               grad_scale, dlogits, dz, gated, loss_sum, correct, counted, soft); break;
+    case 16: hipLaunchKernelGGL((head_fwd_bwd_kernel<16, SOFT>), grid, block, 0, st, z, D, w, bias, labels, B, ncls,
+                                grad_scale, dlogits, dz, gated, loss_sum, correct, counted, soft); break;
+    case 32: hipLaunchKernelGGL((head_fwd_bwd_kernel<32, SOFT>), grid, block, 0, st, z, D, w, bias, labels, B, ncls,
+                                grad_scale, dlogits, dz, gated, loss_sum, correct, counted, soft); break;
     default: return RK_EUNSUPPORTED;
   }
   RK_LAUNCH_CHECK();
   return RK_OK;
+}
+
+extern "C" int rk_head_fwd_bwd(const float* z, int B, int D, const float* w, const float* bias, int NC,
+                               const int* labels, int ncls, float grad_scale, float* dlogits, float* dz, int gated,
+                               float* loss_sum, int* correct, int* counted, void* stream) {
+  return head_fwd_bwd_launch<false>(z, B, D, w, bias, NC, labels, ncls, grad_scale, dlogits, dz, gated, loss_sum,
+                                    correct, counted, HeadSoft<false>{}, stream);
+}
+
+// rk_head_fwd_bwd against the soft target: labels2 [B] int32 (nullable: smoothing only), lam a device float
+// (nullable: 1), 0 <= eps < 1.  A row counts only if both labels are valid, and as correct for the label with
+// the larger share (labels when lam >= 0.5).  lam = 1, eps = 0 gives rk_head_fwd_bwd's dlogits bit for bit.
+extern "C" int rk_head_fwd_bwd_soft(const float* z, int B, int D, const float* w, const float* bias, int NC,
+                                    const int* labels, const int* labels2, const float* lam, float eps, int ncls,
+                                    float grad_scale, float* dlogits, float* dz, int gated, float* loss_sum,
+                                    int* correct, int* counted, void* stream) {
+  if (!(eps >= 0.f && eps < 1.f)) return RK_EBADARG;
+  HeadSoft<true> soft;
+  soft.labels2 = labels2, soft.lam = lam, soft.eps = eps;
+  return head_fwd_bwd_launch<true>(z, B, D, w, bias, NC, labels, ncls, grad_scale, dlogits, dz, gated, loss_sum,
+                                   correct, counted, soft, stream);
 }
 
 // dw [NC][D] = dlogits^T z, db [NC] = column sums of dlogits (nullable), dbh [D] = column sums of dz

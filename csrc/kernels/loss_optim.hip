@@ -14,14 +14,27 @@
 
 namespace {
 
-template <typename DT>  // d(logits) storage: bf16 (bf16 engine) or float (fp32 engine)
+// SOFT (rk_softmax_xent_soft, rk_softmax_xent_f32_soft): the gradient and the loss against the soft target
+//   t_c = (1 - eps) * (lam [c == ya] + (1 - lam) [c == yb]) + eps / ncls
+// (label smoothing, mixup, CutMix) — ya = labels, yb = labels2 (null: smoothing only), lam a device scalar the
+// step prologue wrote (null: 1).  A row is valid only if both labels are; it counts as correct for the label
+// with the larger share.  lam = 1, eps = 0 gives t = onehot(ya) exactly, so the hard kernel's d(logits) bit for bit.
+template <bool SOFT> struct XentSoft {};
+template <> struct XentSoft<true> {
+  const int* labels2;
+  const float* lam;
+  float eps;
+};
+
+template <typename DT, bool SOFT>  // d(logits) storage: bf16 (bf16 engine) or float (fp32 engine)
 __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restrict__ logits, int ldl,
                                                            const int* __restrict__ labels, int B, int ncls,
                                                            int ignore_index, float grad_scale,
                                                            DT* __restrict__ dlogits, int ldd,
                                                            float* __restrict__ probs, float* loss_sum,
                                                            int* correct, int* counted,
-                                                           const float* __restrict__ scale_ptr) {
+                                                           const float* __restrict__ scale_ptr,
+                                                           const XentSoft<SOFT> soft) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= B) return;
@@ -44,16 +57,33 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
   se = wave_sum(se);
   const float lse = mx + __logf(se);
   const int y = labels ? labels[row] : -1;
-  const bool valid = labels && y != ignore_index && y >= 0 && y < ncls;
+  bool valid = labels && y != ignore_index && y >= 0 && y < ncls;
   // scale_ptr: a device factor on the gradient and the loss (the tagger's 1 / #valid tokens of a batch,
   // written with the batch, so a replayed graph takes each batch's mean)
   const float sc = scale_ptr ? scale_ptr[0] : 1.f;
   grad_scale *= sc;
+  // SOFT: the partner label and the two labels' shares (1 and 0 without a partner)
+  int y2 = y;
+  float wa = 1.f, wb = 0.f;
+  if constexpr (SOFT) {
+    if (soft.labels2) {
+      y2 = soft.labels2[row];
+      valid = valid && y2 != ignore_index && y2 >= 0 && y2 < ncls;
+      wa = soft.lam ? soft.lam[0] : 1.f;
+      wb = 1.f - wa;
+    }
+  }
   if (dlogits) {
     DT* dr = dlogits + (long long)row * ldd;
     for (int c = lane; c < ldd; c += 64) {
       float g = 0.f;
-      if (valid && c < ncls) g = (__expf(lr[c] - lse) - (c == y ? 1.f : 0.f)) * grad_scale;
+      if constexpr (SOFT) {
+        const float t = (1.f - soft.eps) * (wa * (c == y ? 1.f : 0.f) + wb * (c == y2 ? 1.f : 0.f)) +
+                        soft.eps / (float)ncls;
+        if (valid && c < ncls) g = (__expf(lr[c] - lse) - t) * grad_scale;
+      } else {
+        if (valid && c < ncls) g = (__expf(lr[c] - lse) - (c == y ? 1.f : 0.f)) * grad_scale;
+      }
       dr[c] = (DT)g;
     }
   }
@@ -61,10 +91,25 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
     float* pr = probs + (long long)row * ncls;
     for (int c = lane; c < ncls; c += 64) pr[c] = __expf(lr[c] - lse);
   }
-  if (lane == 0 && valid) {
-    if (loss_sum) atomicAdd(loss_sum, (lse - lr[y]) * sc);
-    if (correct) atomicAdd(correct, amax == y ? 1 : 0);
-    if (counted) atomicAdd(counted, 1);
+  if constexpr (SOFT) {
+    // loss = lse - (1 - eps) (wa l_ya + wb l_yb) - eps / ncls * sum_c l_c: lane partials in class order, then
+    // the wave's butterfly — a fixed order
+    float ls = 0.f;
+    for (int c = lane; c < ncls; c += 64) ls += lr[c];
+    ls = wave_sum(ls);
+    if (lane == 0 && valid) {
+      if (loss_sum)
+        atomicAdd(loss_sum,
+                  (lse - (1.f - soft.eps) * (wa * lr[y] + wb * lr[y2]) - soft.eps / (float)ncls * ls) * sc);
+      if (correct) atomicAdd(correct, amax == (wa >= 0.5f ? y : y2) ? 1 : 0);
+      if (counted) atomicAdd(counted, 1);
+    }
+  } else {
+    if (lane == 0 && valid) {
+      if (loss_sum) atomicAdd(loss_sum, (lse - lr[y]) * sc);
+      if (correct) atomicAdd(correct, amax == y ? 1 : 0);
+      if (counted) atomicAdd(counted, 1);
+    }
   }
 }
 
@@ -335,7 +380,52 @@ struct AugDraw {
   int dy, dx, flip;
 };
 
-template <bool AUG>
+// MIX != 0 (rk_gather_batch_mix) is the same prologue mixing every output row b with its partner, the row of
+// sched[step][(b + 1) % B] (clamped like the primary; each of the two augmented by its own row's draw when AUG):
+//   MIX = 1 (blend, mixup):  out = lam * a + (1 - lam) * p per element in fp32, stored in the data's dtype — two
+//     products and one sum, each rounded once, so lam = 1 gives a and lam = 0 gives p for finite images
+//   MIX = 2 (box, CutMix):   out[y, x] = p[y, x] inside the box (y0, y1, x0, x1), a[y, x] outside: one load
+// lam = lam_table[step] (clamped to [0, 1]; NaN reads 0) and the box = box_table[step] (clamped to the image) ride
+// next to lr_table; the prologue also leaves out_y2[b] = labels[partner row] and *lam_out = lam for the soft-target
+// loss later in the step.  rafiki_amd/ops/mix.py is the host twin.
+template <int MIX> struct GatherMix {
+  int H, W, vpp, is_bf16;
+  const float* lam_table;  // [nsteps]
+  const int* box_table;    // [nsteps][4], MIX = 2
+  int* out_y2;
+  float* lam_out;
+};
+template <> struct GatherMix<0> {};
+
+// lam * a + oml * p with each product and the sum rounded once: contraction into an FMA is off here, so the host
+// twin's separate fp32 operations give the same bits
+RK_DEV float blend1(float lam, float a, float oml, float p) {
+#pragma clang fp contract(off)
+  const float ta = lam * a, tp = oml * p;
+  return ta + tp;
+}
+
+// one 16-byte vector of the two images, blended: 4 fp32 or 8 bf16 elements
+RK_DEV uint4 blend_vec(uint4 a, uint4 p, float lam, float oml, int is_bf16) {
+  uint4 o;
+  const uint32_t* au = (const uint32_t*)&a;
+  const uint32_t* pu = (const uint32_t*)&p;
+  uint32_t* ou = (uint32_t*)&o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (is_bf16) {
+      const float lo = blend1(lam, __uint_as_float(au[e] << 16), oml, __uint_as_float(pu[e] << 16));
+      const float hi = blend1(lam, __uint_as_float(au[e] & 0xffff0000u), oml, __uint_as_float(pu[e] & 0xffff0000u));
+      const bf16 bl = (bf16)lo, bh = (bf16)hi;   // round to nearest even
+      ou[e] = (uint32_t) * (const unsigned short*)&bl | ((uint32_t) * (const unsigned short*)&bh << 16);
+    } else {
+      ou[e] = __float_as_uint(blend1(lam, __uint_as_float(au[e]), oml, __uint_as_float(pu[e])));
+    }
+  }
+  return o;
+}
+
+template <bool AUG, int MIX>
 __global__ __launch_bounds__(256) void gather_batch_kernel(const uint4* __restrict__ data, long long row_vec,
                                                            const int* __restrict__ labels,
                                                            const long long* __restrict__ sched,
@@ -344,7 +434,7 @@ __global__ __launch_bounds__(256) void gather_batch_kernel(const uint4* __restri
                                                            double* __restrict__ zero, long long zero_n,
                                                            int* __restrict__ done, const float* __restrict__ lr_table,
                                                            float* __restrict__ lr_out, int nsteps, long long nrows,
-                                                           const GatherAug<AUG> aug) {
+                                                           const GatherAug<AUG> aug, const GatherMix<MIX> mix) {
   // the schedule holds nsteps rows: a counter past it wraps around (warm-up runs, extra replays) instead
   // of reading beyond the buffers; row indices outside the dataset read row 0
   const long long step = (long long)((unsigned)*counter % (unsigned)nsteps);
@@ -352,7 +442,76 @@ __global__ __launch_bounds__(256) void gather_batch_kernel(const uint4* __restri
   if (lr_table && blockIdx.x == 0 && threadIdx.x == 0) *lr_out = lr_table[step];
   const long long total = (long long)B * row_vec;
   const long long gstride = (long long)gridDim.x * blockDim.x;
-  if constexpr (AUG) {
+  if constexpr (MIX != 0) {
+    // The draw table of the augmenting gather, twice: thread t fills the primary's and the partner's entry of
+    // sample b0 + t (without AUG a zero shift and no mirror, so one body serves both).
+    __shared__ AugDraw draws[2][256];
+    const float lam = fminf(fmaxf(mix.lam_table[step], 0.f), 1.f);
+    const float oml = 1.f - lam;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *mix.lam_out = lam;
+    int y0 = 0, y1 = 0, x0 = 0, x1 = 0;
+    if constexpr (MIX == 2) {
+      const int* bx = mix.box_table + 4 * step;
+      y0 = min(max(bx[0], 0), mix.H), y1 = min(max(bx[1], 0), mix.H);
+      x0 = min(max(bx[2], 0), mix.W), x1 = min(max(bx[3], 0), mix.W);
+    }
+    uint32_t ep = 0u;
+    int span = 1;
+    if constexpr (AUG) {
+      ep = aug.epoch ? (uint32_t)*aug.epoch : 0u;
+      span = 2 * aug.pad + 1;
+    }
+    const unsigned line_vec = (unsigned)(mix.W * mix.vpp);
+    for (long long base = (long long)blockIdx.x * blockDim.x; base < total; base += gstride) {
+      const int b0 = (int)(base / row_vec);
+      const int bt = b0 + (int)threadIdx.x;
+      if (bt < B && (long long)bt * row_vec < base + blockDim.x) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          long long src = sched[step * B + (k == 0 ? bt : (bt + 1 == B ? 0 : bt + 1))];
+          if ((unsigned long long)src >= (unsigned long long)nrows) src = 0;
+          AugDraw d;
+          d.src = src, d.dy = 0, d.dx = 0, d.flip = 0;
+          if constexpr (AUG) {
+            const U4 r = philox4x32_10((uint32_t)src, (uint32_t)(src >> 32), aug.stream_id, ep, aug.k0, aug.k1);
+            const int ry = (int)(u01(r.v[0]) * (float)span), rx = (int)(u01(r.v[1]) * (float)span);
+            d.dy = (ry < span ? ry : span - 1) - aug.pad;
+            d.dx = (rx < span ? rx : span - 1) - aug.pad;
+            d.flip = u01(r.v[2]) < aug.flip_p;
+          }
+          draws[k][threadIdx.x] = d;
+        }
+      }
+      __syncthreads();
+      const long long i = base + threadIdx.x;
+      if (i < total) {
+        const int b = (int)(i / row_vec);
+        const unsigned c = (unsigned)(i - (long long)b * row_vec);
+        const unsigned y = c / line_vec, cl = c - y * line_vec;
+        const unsigned x = cl / (unsigned)mix.vpp, v = cl - x * (unsigned)mix.vpp;
+        // one vector of an augmented image: zero outside the source image (the border)
+        auto fetch = [&](int k) {
+          const AugDraw d = draws[k][b - b0];
+          const int sy = (int)y + d.dy, sx = (d.flip ? mix.W - 1 - (int)x : (int)x) + d.dx;
+          uint4 val = {0u, 0u, 0u, 0u};
+          if ((unsigned)sy < (unsigned)mix.H && (unsigned)sx < (unsigned)mix.W)
+            val = data[d.src * row_vec + ((long long)sy * mix.W + sx) * mix.vpp + v];
+          return val;
+        };
+        if constexpr (MIX == 1) {
+          out[i] = blend_vec(fetch(0), fetch(1), lam, oml, mix.is_bf16);
+        } else {
+          const bool inside = (int)y >= y0 && (int)y < y1 && (int)x >= x0 && (int)x < x1;
+          out[i] = fetch(inside ? 1 : 0);
+        }
+        if (c == 0) {
+          out_y[b] = labels[draws[0][b - b0].src];
+          mix.out_y2[b] = labels[draws[1][b - b0].src];
+        }
+      }
+      __syncthreads();  // every thread has its draws before the next trip overwrites the table
+    }
+  } else if constexpr (AUG) {
     // The 10 Philox rounds run once per (block, sample), not once per vector: a block's 256 consecutive
     // vectors start in sample b0 and touch at most 256 samples, thread t draws for sample b0 + t and every
     // thread then picks its sample's draw out of LDS.  The trip count is the same for a whole block.
@@ -574,9 +733,9 @@ extern "C" int rk_softmax_xent(const float* logits, int ldl, const int* labels, 
                                float grad_scale, void* dlogits, int ldd, float* probs, float* loss_sum, int* correct,
                                int* counted, void* stream) {
   if (B <= 0) return RK_OK;
-  hipLaunchKernelGGL(softmax_xent_kernel<bf16>, dim3(rk_cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream, logits, ldl,
-                     labels, B, ncls, ignore_index, grad_scale, (bf16*)dlogits, ldd, probs, loss_sum, correct, counted,
-                     nullptr);
+  hipLaunchKernelGGL((softmax_xent_kernel<bf16, false>), dim3(rk_cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream,
+                     logits, ldl, labels, B, ncls, ignore_index, grad_scale, (bf16*)dlogits, ldd, probs, loss_sum,
+                     correct, counted, nullptr, XentSoft<false>{});
   RK_LAUNCH_CHECK();
   return RK_OK;
 }
@@ -586,11 +745,44 @@ extern "C" int rk_softmax_xent_f32(const float* logits, int ldl, const int* labe
                                    float grad_scale, float* dlogits, int ldd, float* probs, float* loss_sum,
                                    int* correct, int* counted, void* stream) {
   if (B <= 0) return RK_OK;
-  hipLaunchKernelGGL(softmax_xent_kernel<float>, dim3(rk_cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream, logits, ldl,
-                     labels, B, ncls, ignore_index, grad_scale, dlogits, ldd, probs, loss_sum, correct, counted,
-                     nullptr);
+  hipLaunchKernelGGL((softmax_xent_kernel<float, false>), dim3(rk_cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream,
+                     logits, ldl, labels, B, ncls, ignore_index, grad_scale, dlogits, ldd, probs, loss_sum, correct,
+                     counted, nullptr, XentSoft<false>{});
   RK_LAUNCH_CHECK();
   return RK_OK;
+}
+
+// rk_softmax_xent / rk_softmax_xent_f32 against the soft target: labels2 [B] int32 (nullable: smoothing only), lam
+// a device float (nullable: 1), 0 <= eps < 1
+template <typename DT>
+static int softmax_xent_soft_launch(const float* logits, int ldl, const int* labels, const int* labels2,
+                                    const float* lam, float eps, int B, int ncls, int ignore_index, float grad_scale,
+                                    DT* dlogits, int ldd, float* loss_sum, int* correct, int* counted, void* stream) {
+  if (!(eps >= 0.f && eps < 1.f) || ncls <= 0 || !labels) return RK_EBADARG;
+  if (B <= 0) return RK_OK;
+  XentSoft<true> soft;
+  soft.labels2 = labels2, soft.lam = lam, soft.eps = eps;
+  hipLaunchKernelGGL((softmax_xent_kernel<DT, true>), dim3(rk_cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream, logits,
+                     ldl, labels, B, ncls, ignore_index, grad_scale, dlogits, ldd, nullptr, loss_sum, correct,
+                     counted, nullptr, soft);
+  RK_LAUNCH_CHECK();
+  return RK_OK;
+}
+
+extern "C" int rk_softmax_xent_soft(const float* logits, int ldl, const int* labels, const int* labels2,
+                                    const float* lam, float eps, int B, int ncls, int ignore_index, float grad_scale,
+                                    void* dlogits, int ldd, float* loss_sum, int* correct, int* counted,
+                                    void* stream) {
+  return softmax_xent_soft_launch<bf16>(logits, ldl, labels, labels2, lam, eps, B, ncls, ignore_index, grad_scale,
+                                        (bf16*)dlogits, ldd, loss_sum, correct, counted, stream);
+}
+
+extern "C" int rk_softmax_xent_f32_soft(const float* logits, int ldl, const int* labels, const int* labels2,
+                                        const float* lam, float eps, int B, int ncls, int ignore_index,
+                                        float grad_scale, float* dlogits, int ldd, float* loss_sum, int* correct,
+                                        int* counted, void* stream) {
+  return softmax_xent_soft_launch<float>(logits, ldl, labels, labels2, lam, eps, B, ncls, ignore_index, grad_scale,
+                                         dlogits, ldd, loss_sum, correct, counted, stream);
 }
 
 // fp32 d(logits) with a device scale factor: gradient and loss both times *scale (mean over a
@@ -599,8 +791,9 @@ extern "C" int rk_softmax_xent_f32s(const float* logits, int ldl, const int* lab
                                     int ignore_index, const float* scale, float* dlogits, int ldd, float* loss_sum,
                                     void* stream) {
   if (B <= 0) return RK_OK;
-  hipLaunchKernelGGL(softmax_xent_kernel<float>, dim3(rk_cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream, logits, ldl,
-                     labels, B, ncls, ignore_index, 1.0f, dlogits, ldd, nullptr, loss_sum, nullptr, nullptr, scale);
+  hipLaunchKernelGGL((softmax_xent_kernel<float, false>), dim3(rk_cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream,
+                     logits, ldl, labels, B, ncls, ignore_index, 1.0f, dlogits, ldd, nullptr, loss_sum, nullptr,
+                     nullptr, scale, XentSoft<false>{});
   RK_LAUNCH_CHECK();
   return RK_OK;
 }
@@ -847,9 +1040,9 @@ extern "C" int rk_gather_batch(const void* data, long long row_bytes, const int*
   if (row_bytes % 16 || zero_n < 0 || (zero_n && !zero) || (lr_table && !lr_out)) return RK_EUNSUPPORTED;
   if (nsteps <= 0 || nrows <= 0) return RK_EBADARG;
   const long long rv = row_bytes / 16;
-  hipLaunchKernelGGL(gather_batch_kernel<false>, dim3(grid_for((long long)B * rv, 2048)), dim3(256), 0,
+  hipLaunchKernelGGL((gather_batch_kernel<false, 0>), dim3(grid_for((long long)B * rv, 2048)), dim3(256), 0,
                      (hipStream_t)stream, (const uint4*)data, rv, labels, sched, counter, B, (uint4*)out, out_y, zero,
-                     zero_n, done, lr_table, lr_out, nsteps, nrows, GatherAug<false>{});
+                     zero_n, done, lr_table, lr_out, nsteps, nrows, GatherAug<false>{}, GatherMix<0>{});
   RK_LAUNCH_CHECK();
   return RK_OK;
 }
@@ -872,9 +1065,72 @@ extern "C" int rk_gather_batch_aug(const void* data, long long row_bytes, const 
   GatherAug<true> aug;
   aug.H = H, aug.W = W, aug.vpp = vpp, aug.pad = pad, aug.flip_p = flip_p;
   aug.k0 = (uint32_t)seed, aug.k1 = (uint32_t)(seed >> 32), aug.stream_id = (uint32_t)stream_id, aug.epoch = epoch;
-  hipLaunchKernelGGL(gather_batch_kernel<true>, dim3(grid_for((long long)B * rv, 2048)), dim3(256), 0,
+  hipLaunchKernelGGL((gather_batch_kernel<true, 0>), dim3(grid_for((long long)B * rv, 2048)), dim3(256), 0,
                      (hipStream_t)stream, (const uint4*)data, rv, labels, sched, counter, B, (uint4*)out, out_y, zero,
-                     zero_n, done, lr_table, lr_out, nsteps, nrows, aug);
+                     zero_n, done, lr_table, lr_out, nsteps, nrows, aug, GatherMix<0>{});
+  RK_LAUNCH_CHECK();
+  return RK_OK;
+}
+
+// rk_gather_batch (augment = 0; pad and flip_p must then be 0) or rk_gather_batch_aug (augment = 1) with the mixing
+// of gather_batch_kernel<., MIX>: kind 1 blends (mixup), kind 2 copies a box (CutMix).  lam_table [nsteps] fp32,
+// box_table [nsteps][4] int32 (y0, y1, x0, x1), half-open (kind 2; clamped to the image by the kernel), out_y2 [B]
+// int32 = the partner's labels, lam_out a device float = the step's lam; is_bf16: the element type of a vector
+// (8 bf16 or 4 fp32; a copy needs none, the blend computes).  The geometry is checked as rk_gather_batch_aug's.
+template <bool AUG, int MIX>
+static void gather_mix_launch(dim3 grid, hipStream_t st, const uint4* data, long long rv, const int* labels,
+                              const long long* sched, int* counter, int B, uint4* out, int* out_y, double* zero,
+                              long long zero_n, int* done, const float* lr_table, float* lr_out, int nsteps,
+                              long long nrows, const GatherAug<true>& a, const GatherMix<MIX>& mix) {
+  if constexpr (AUG) {
+    hipLaunchKernelGGL((gather_batch_kernel<true, MIX>), grid, dim3(256), 0, st, data, rv, labels, sched, counter, B,
+                       out, out_y, zero, zero_n, done, lr_table, lr_out, nsteps, nrows, a, mix);
+  } else {
+    hipLaunchKernelGGL((gather_batch_kernel<false, MIX>), grid, dim3(256), 0, st, data, rv, labels, sched, counter, B,
+                       out, out_y, zero, zero_n, done, lr_table, lr_out, nsteps, nrows, GatherAug<false>{}, mix);
+  }
+}
+
+extern "C" int rk_gather_batch_mix(const void* data, long long row_bytes, const int* labels, const long long* sched,
+                                   int* counter, int B, void* out, int* out_y, double* zero, long long zero_n,
+                                   int* done, const float* lr_table, float* lr_out, int nsteps, long long nrows,
+                                   int H, int W, int vpp, int augment, int pad, float flip_p,
+                                   unsigned long long seed, unsigned int stream_id, const int* epoch, int kind,
+                                   int is_bf16, const float* lam_table, const int* box_table, int* out_y2,
+                                   float* lam_out, void* stream) {
+  if (zero_n < 0 || (zero_n && !zero) || (lr_table && !lr_out)) return RK_EUNSUPPORTED;
+  if (H <= 0 || W <= 0 || vpp <= 0 || H > 65535 || W > 65535 || vpp > 4096) return RK_EUNSUPPORTED;
+  if (row_bytes > 16LL * 0x7fffffff || row_bytes != 16LL * H * W * vpp) return RK_EUNSUPPORTED;
+  if (pad < 0 || pad >= (H < W ? H : W) || !(flip_p >= 0.f && flip_p <= 1.f)) return RK_EUNSUPPORTED;
+  if (!augment && (pad != 0 || flip_p != 0.f)) return RK_EUNSUPPORTED;
+  if ((kind != 1 && kind != 2) || (kind == 2 && !box_table)) return RK_EUNSUPPORTED;
+  if (!data || !labels || !sched || !counter || !out || !out_y || !lam_table || !out_y2 || !lam_out) return RK_EBADARG;
+  if (nsteps <= 0 || nrows <= 0 || B <= 0) return RK_EBADARG;
+  const long long rv = row_bytes / 16;
+  GatherAug<true> aug;
+  aug.H = H, aug.W = W, aug.vpp = vpp, aug.pad = pad, aug.flip_p = flip_p;
+  aug.k0 = (uint32_t)seed, aug.k1 = (uint32_t)(seed >> 32), aug.stream_id = (uint32_t)stream_id, aug.epoch = epoch;
+  const dim3 grid(grid_for((long long)B * rv, 2048));
+  const hipStream_t st = (hipStream_t)stream;
+  const uint4* d = (const uint4*)data;
+  uint4* o = (uint4*)out;
+  if (kind == 1) {
+    GatherMix<1> mix;
+    mix.H = H, mix.W = W, mix.vpp = vpp, mix.is_bf16 = is_bf16 != 0;
+    mix.lam_table = lam_table, mix.box_table = box_table, mix.out_y2 = out_y2, mix.lam_out = lam_out;
+    if (augment) gather_mix_launch<true, 1>(grid, st, d, rv, labels, sched, counter, B, o, out_y, zero, zero_n, done,
+                                            lr_table, lr_out, nsteps, nrows, aug, mix);
+    else gather_mix_launch<false, 1>(grid, st, d, rv, labels, sched, counter, B, o, out_y, zero, zero_n, done,
+                                     lr_table, lr_out, nsteps, nrows, aug, mix);
+  } else {
+    GatherMix<2> mix;
+    mix.H = H, mix.W = W, mix.vpp = vpp, mix.is_bf16 = is_bf16 != 0;
+    mix.lam_table = lam_table, mix.box_table = box_table, mix.out_y2 = out_y2, mix.lam_out = lam_out;
+    if (augment) gather_mix_launch<true, 2>(grid, st, d, rv, labels, sched, counter, B, o, out_y, zero, zero_n, done,
+                                            lr_table, lr_out, nsteps, nrows, aug, mix);
+    else gather_mix_launch<false, 2>(grid, st, d, rv, labels, sched, counter, B, o, out_y, zero, zero_n, done,
+                                     lr_table, lr_out, nsteps, nrows, aug, mix);
+  }
   RK_LAUNCH_CHECK();
   return RK_OK;
 }

@@ -122,7 +122,7 @@ class ConvNetEngine:
                  bn_eps: float = 1e-5, bn_momentum: float = 0.1, optimizer: str = 'sgd', lr: float = 0.05,
                  momentum: float = 0.9, weight_decay: float = 5e-4, nesterov: bool = True,
                  betas=(0.9, 0.999), input_bn: bool = False, dtype: Optional[str] = None, bn: bool = True,
-                 augment: Optional[dict] = None):
+                 augment: Optional[dict] = None, mix: Optional[dict] = None, label_smoothing: float = 0.0):
         self.device = torch.device(device)
         self.dtype = dtype or default_dtype()
         if self.dtype not in DTYPES:
@@ -158,6 +158,26 @@ class ConvNetEngine:
             self.augment = {'pad': pad, 'flip': flip}
         self._aug_seed = int(seed)
         self._aug_epoch = self._aug_ctr0 = None
+        # mix {'kind': 'mixup' | 'cutmix', 'alpha': > 0, 'prob': 0..1}: every training row is blended with (mixup)
+        # or gets a box of (cutmix) the next row of its batch, one (lam, box) per step from the epoch's plan
+        # (ops/mix.py) — in the scheduled graph's prologue launch or by mix_batch; label_smoothing eps: the
+        # target's share spread over all classes.  Either one sends the step through the soft-target loss kernels
+        self.mix = None
+        if mix is not None:
+            from ..ops.mix import KINDS
+            if self.flat_input:
+                raise ValueError('mix needs image inputs (conv blocks), not a flat-input net')
+            kind, alpha, prob = mix.get('kind'), float(mix.get('alpha', 1.0)), float(mix.get('prob', 1.0))
+            if set(mix) - {'kind', 'alpha', 'prob'} or kind not in KINDS or not alpha > 0.0 or \
+                    not math.isfinite(alpha) or not 0.0 <= prob <= 1.0:
+                raise ValueError("mix must be {{'kind': one of {}, 'alpha': > 0, 'prob': 0..1}}, got {!r}".format(
+                    KINDS, mix))
+            self.mix = {'kind': kind, 'alpha': alpha, 'prob': prob}
+        self.label_smoothing = float(label_smoothing)
+        if not 0.0 <= self.label_smoothing < 1.0:
+            raise ValueError('label_smoothing must lie in [0, 1), got {!r}'.format(label_smoothing))
+        self.soft = self.mix is not None or self.label_smoothing > 0.0
+        self._static_y2 = self._lam = self._lam_table = self._box_table = None
         # any image size: power-of-two maps use the shift-decoded (and LDS-DMA) gather, others the
         # reciprocal-decoded register-staged gather (VGG16 at 48x48: 48/24/12/6/3)
         flat = FlatParams(self.device, seed, compute_bf16=not self.f32)
@@ -344,8 +364,12 @@ class ConvNetEngine:
             fc_in.append(z)
         logits = F.linear(z, fl.wb('out.w'), fl.w('out.b'), out_dtype=torch.float32)
         dlogits = torch.empty((B, self.ncls_p), dtype=torch.bfloat16, device=self.device)
-        F.softmax_xent(logits, labels, self.num_classes, dlogits=dlogits, loss_sum=self.loss_sum,
-                       correct=self.correct, counted=self.seen)
+        if self.soft:
+            F.softmax_xent_soft(logits, labels, self.num_classes, dlogits=dlogits, loss_sum=self.loss_sum,
+                                correct=self.correct, counted=self.seen, **self._soft_args(B))
+        else:
+            F.softmax_xent(logits, labels, self.num_classes, dlogits=dlogits, loss_sum=self.loss_sum,
+                           correct=self.correct, counted=self.seen)
         # ---- backward
         F.linear_dw(dlogits, fc_in[-1], out=fl.g('out.w'))
         F.colsum(dlogits, fl.g('out.b'))
@@ -475,8 +499,13 @@ class ConvNetEngine:
             # hidden layer's bias gradients in a second (csrc/kernels/head.hip)
             gated = k_top >= 0
             dz = torch.empty((B, self.d_last), dtype=torch.float32, device=self.device)
-            S.head_fwd_bwd(z, fl.w('out.w'), fl.w('out.b'), labels, self.num_classes, dlogits=dlogits, dz=dz,
-                           gated=gated, loss_sum=self.loss_sum, correct=self.correct, counted=self.seen)
+            if self.soft:
+                S.head_fwd_bwd_soft(z, fl.w('out.w'), fl.w('out.b'), labels, self.num_classes, dlogits=dlogits,
+                                    dz=dz, gated=gated, loss_sum=self.loss_sum, correct=self.correct,
+                                    counted=self.seen, **self._soft_args(B))
+            else:
+                S.head_fwd_bwd(z, fl.w('out.w'), fl.w('out.b'), labels, self.num_classes, dlogits=dlogits, dz=dz,
+                               gated=gated, loss_sum=self.loss_sum, correct=self.correct, counted=self.seen)
             S.head_dw(z, dlogits, dz, dw=fl.g('out.w'), db=fl.g('out.b'),
                       dbh=fl.g(self.fcs[k_top][0] + '.b') if gated else None)
             d = dz
@@ -487,8 +516,12 @@ class ConvNetEngine:
                 wname = None   # dz is already the gradient of the flattened features
         else:
             logits = S.linear(z, fl.w('out.w'), fl.w('out.b'))
-            S.softmax_xent(logits, labels, self.num_classes, dlogits=dlogits, loss_sum=self.loss_sum,
-                           correct=self.correct, counted=self.seen)
+            if self.soft:
+                S.softmax_xent_soft(logits, labels, self.num_classes, dlogits=dlogits, loss_sum=self.loss_sum,
+                                    correct=self.correct, counted=self.seen, **self._soft_args(B))
+            else:
+                S.softmax_xent(logits, labels, self.num_classes, dlogits=dlogits, loss_sum=self.loss_sum,
+                               correct=self.correct, counted=self.seen)
             # ---- backward
             S.linear_dw(dlogits, fc_in[-1], out=fl.g('out.w'))
             S.colsum(dlogits, fl.g('out.b'))
@@ -594,8 +627,12 @@ class ConvNetEngine:
 
     # ------------------------------------------------------------------------ reference path
     def reference_loss(self, x_nhwc: torch.Tensor, labels: torch.Tensor, params: Optional[dict] = None,
-                       training=True, update_running=False, emulate_bf16=False):
+                       training=True, update_running=False, emulate_bf16=False, labels2=None, lam=None,
+                       smoothing=0.0):
         """Pure PyTorch fp32 forward of the same network (NCHW internally). Returns (loss, logits).
+
+        ``labels2`` / ``lam`` / ``smoothing``: the soft target (1 - smoothing) * (lam * onehot(labels) +
+        (1 - lam) * onehot(labels2)) + smoothing / num_classes; the defaults give the hard-label loss.
 
         ``emulate_bf16`` rounds (straight-through) at exactly the points where the GPU engine stores
         bf16: weights, conv outputs, block outputs and FC hidden activations — the tight oracle for
@@ -650,8 +687,15 @@ class ConvNetEngine:
             h = rnd(torch.relu(h @ rndw(P[name + '.w']).t() + P[name + '.b']))
         logits = (h @ rndw(P['out.w']).t() + P['out.b'])[:, :self.num_classes]
         logits = _bf16_grad(logits) if emulate_bf16 and emulate_bf16 != 'fwd' else logits
-        loss = TF.cross_entropy(logits, labels.long()) if labels is not None else None
-        return loss, logits
+        if labels is None:
+            return None, logits
+        if labels2 is None and lam is None and smoothing == 0.0:
+            return TF.cross_entropy(logits, labels.long()), logits
+        lam = 1.0 if lam is None or labels2 is None else torch.as_tensor(lam).to(logits).reshape(())
+        one = TF.one_hot(labels.long(), self.num_classes).to(logits)
+        two = one if labels2 is None else TF.one_hot(labels2.long(), self.num_classes).to(logits)
+        target = (1.0 - smoothing) * (lam * one + (1.0 - lam) * two) + smoothing / self.num_classes
+        return -(target * torch.log_softmax(logits, 1)).sum(1).mean(), logits
 
     def _train_step_cpu(self, x, labels):
         self._fwd_bwd_cpu(x, labels)
@@ -660,13 +704,19 @@ class ConvNetEngine:
     def _fwd_bwd_cpu(self, x, labels):
         fl = self.flat
         params = {n: fl.w(n).detach().clone().requires_grad_(True) for n in fl.names()}
-        loss, logits = self.reference_loss(x, labels, params, training=True, update_running=True)
+        soft, counts_for = {}, labels
+        if self.soft:
+            sa = self._soft_args(x.shape[0])
+            soft = dict(labels2=sa['labels2'], lam=sa['lam'], smoothing=sa['eps'])
+            if sa['labels2'] is not None and float(sa['lam']) < 0.5:
+                counts_for = sa['labels2']      # a prediction counts as correct for the label with the larger share
+        loss, logits = self.reference_loss(x, labels, params, training=True, update_running=True, **soft)
         grads = torch.autograd.grad(loss, [params[n] for n in fl.names()])
         for n, g in zip(fl.names(), grads):
             fl.g(n).copy_(g)
         with torch.no_grad():
             self.loss_sum += loss.detach() * x.shape[0]
-            self.correct += (logits.argmax(1) == labels.long()).sum().to(torch.int32)
+            self.correct += (logits.argmax(1) == counts_for.long()).sum().to(torch.int32)
             self.seen += x.shape[0]
 
     # --------------------------------------------------------------------------- public API
@@ -689,6 +739,8 @@ class ConvNetEngine:
             return None
         self._static_x = torch.zeros(self.input_shape(batch_size), dtype=self.act_dtype, device=self.device)
         self._static_y = torch.zeros((batch_size,), dtype=torch.int32, device=self.device)
+        if self.mix is not None:
+            self._mix_buffers(batch_size)   # the captured soft loss reads y2 / lam, mix_batch fills them per step
         # warm the allocator / library outside capture; these steps use zero inputs and are
         # undone by restoring the parameter state afterwards.
         snap = [self.flat.master.clone(), self.running.clone()]
@@ -735,7 +787,14 @@ class ConvNetEngine:
         opt_bumps = isinstance(self.opt, FlatSGD)
 
         gather, aug = F.gather_batch, {}
-        if self.augment is not None:
+        if self.mix is not None:
+            # per-step (lam, box) tables next to the LR table: set_schedule uploads an epoch's plan, the prologue
+            # reads row *ctr.  Until then every step is unmixed (lam 1, empty box)
+            self._mix_buffers(batch_size)
+            self._lam_table = torch.ones(max_steps, dtype=torch.float32, device=self.device)
+            self._box_table = torch.zeros((max_steps, 4), dtype=torch.int32, device=self.device)
+            gather, aug = F.gather_batch_mix, self._mix_args(self._lam_table, self._box_table)
+        elif self.augment is not None:
             gather, aug = F.gather_batch_aug, self._aug_args()
 
         def body():
@@ -786,9 +845,76 @@ class ConvNetEngine:
             self._lr_table[:len(lr_scales)].copy_(torch.as_tensor(lr_scales, dtype=torch.float32))
         if epoch is not None and self.augment is not None:
             self._aug_epoch.fill_(int(epoch))
+        if epoch is not None and self.mix is not None:
+            lam, box = self._mix_plan(epoch, idx.shape[0])
+            self._lam_table[:idx.shape[0]].copy_(torch.from_numpy(lam[:idx.shape[0]]))
+            self._box_table[:idx.shape[0]].copy_(torch.from_numpy(box[:idx.shape[0]]))
 
     def replay(self):
         self._sched_graph.replay()
+
+    # ------------------------------------------------------------------------ soft targets
+    def _mix_buffers(self, B):
+        """The partner labels [B] and the step's lam [1] the soft loss reads, made once per batch size."""
+        if self._static_y2 is None or self._static_y2.shape[0] != B:
+            self._static_y2 = torch.zeros((B,), dtype=torch.int32, device=self.device)
+            self._lam = torch.ones(1, dtype=torch.float32, device=self.device)
+            self._mb_lam = torch.ones(1, dtype=torch.float32, device=self.device)
+            self._mb_box = torch.zeros((1, 4), dtype=torch.int32, device=self.device)
+
+    def _mix_plan(self, epoch, steps):
+        """(lam, box) of the first ``steps`` steps of ``epoch`` (ops/mix.plan; a longer plan extends a shorter
+        one), kept for the epoch."""
+        from ..ops.mix import plan
+        c = getattr(self, '_plan_cache', None)
+        if c is None or c[0] != int(epoch) or len(c[1]) < steps:
+            m = self.mix
+            c = self._plan_cache = (int(epoch),) + plan(self._aug_seed, epoch, steps, m['kind'], m['alpha'],
+                                                          m['prob'], self.image_size, self.image_size)
+        return c[1], c[2]
+
+    def _mix_args(self, lam_table, box_table):
+        """The arguments of F.gather_batch_mix past the prologue's own."""
+        aug = self._aug_args() if self.augment is not None else {}
+        return dict(kind=self.mix['kind'], lam_table=lam_table, box_table=box_table, out_y2=self._static_y2,
+                    lam_out=self._lam, **aug)
+
+    def _soft_args(self, B):
+        """labels2 / lam / eps of the soft-target loss: the buffers the mixing prologue or mix_batch filled."""
+        if self.mix is None:
+            return dict(labels2=None, lam=None, eps=self.label_smoothing)
+        if self._static_y2 is None or self._static_y2.shape[0] != B:
+            raise RuntimeError('mix: no mixed batch of {} rows (mix_batch or capture_scheduled first)'.format(B))
+        return dict(labels2=self._static_y2, lam=self._lam, eps=self.label_smoothing)
+
+    def mix_batch(self, data, labels, idx, epoch, step_in_epoch, out_x, out_y):
+        """out_x / out_y and the engine's partner-label and lam buffers = what the scheduled graph's mixing
+        prologue gives for rows ``idx`` at step ``step_in_epoch`` of ``epoch`` (augmented first when the engine
+        augments): on the GPU the same kernel over a one-row schedule, on the CPU its host twin.  For the loops
+        that feed the step themselves (``step_graph`` / ``train_step``)."""
+        if self.mix is None:
+            raise RuntimeError('mix_batch on an engine built without mix')
+        lam, box = self._mix_plan(epoch, int(step_in_epoch) + 1)
+        lam, box = float(lam[step_in_epoch]), box[step_in_epoch]
+        self._mix_buffers(out_x.shape[0])
+        if self.device.type == 'cuda':
+            self._mb_lam.fill_(lam)
+            self._mb_box.copy_(torch.from_numpy(box).view(1, 4))
+            args = self._mix_args(self._mb_lam, self._mb_box)
+            if self.augment is not None:
+                self._aug_epoch.fill_(int(epoch))
+            elif self._aug_ctr0 is None:
+                self._aug_ctr0 = torch.zeros(1, dtype=torch.int32, device=self.device)
+            return F.gather_batch_mix(data, labels, idx.reshape(1, -1), self._aug_ctr0, out_x, out_y, **args)
+        from ..ops import mix as M
+        idx = torch.as_tensor(idx, dtype=torch.int64).reshape(-1)
+        idx = torch.where((idx < 0) | (idx >= data.shape[0]), torch.zeros_like(idx), idx)
+        out_x.copy_(M.apply(data, idx, self.mix['kind'], lam, box, augment=self.augment, seed=self._aug_seed,
+                            epoch=epoch))
+        out_y.copy_(labels[idx])
+        self._static_y2.copy_(labels[torch.roll(idx, -1)])
+        self._lam.fill_(lam)
+        return out_x
 
     def _aug_args(self):
         """The augmentation arguments of F.gather_batch_aug; the device epoch word is made on first use."""
@@ -999,7 +1125,8 @@ class ConvNetEngine:
         finished trial can stay resident in HBM for serving at its inference footprint."""
         from ..ops.graphs import quiesced
         with quiesced():
-            for a in ('_graph', '_sched_graph', '_static_x', '_static_y', '_sched', '_ctr', '_ww', '_wt'):
+            for a in ('_graph', '_sched_graph', '_static_x', '_static_y', '_sched', '_ctr', '_ww', '_wt',
+                      '_static_y2', '_lam', '_lam_table', '_box_table', '_mb_lam', '_mb_box'):
                 if hasattr(self, a):
                     setattr(self, a, None)
             self.opt = None

@@ -67,10 +67,28 @@ class NativeImageClassifier(BaseModel):
         pad = max(0, min(int(self._knobs.get('augment_pad', 4)), self.image_size - 1))
         return {'pad': pad if 'crop' in mode else 0, 'flip': 0.5 if 'flip' in mode else 0.0}
 
-    def _build(self, num_classes, channels, dtype=None, augment=None):
+    MIX_MODES = ('none', 'mixup', 'cutmix')
+
+    def _regularisers(self):
+        """The engine's ``mix`` and ``label_smoothing`` arguments from the knobs ``mix`` (one of MIX_MODES, default
+        'none'), ``mix_alpha`` (the Beta parameter, default 1.0), ``mix_prob`` (the share of mixed steps, default 1.0
+        for mixup and 0.5 for cutmix) and ``label_smoothing`` (default 0.0).  Training only."""
+        mode = self._knobs.get('mix', 'none')
+        if mode not in self.MIX_MODES:
+            raise ValueError('mix must be one of {}, got {!r}'.format(self.MIX_MODES, mode))
+        out = {}
+        if mode != 'none':
+            out['mix'] = {'kind': mode, 'alpha': float(self._knobs.get('mix_alpha', 1.0)),
+                          'prob': float(self._knobs.get('mix_prob', 1.0 if mode == 'mixup' else 0.5))}
+        if float(self._knobs.get('label_smoothing', 0.0)) != 0.0:
+            out['label_smoothing'] = float(self._knobs['label_smoothing'])
+        return out
+
+    def _build(self, num_classes, channels, dtype=None, augment=None, **regularisers):
         kw = self._engine_kwargs(num_classes, channels, self.image_size)
         if augment is not None:
             kw['augment'] = augment
+        kw.update(regularisers)
         # compute dtype: fp32 (reference precision) unless the trial / RAFIKI_DTYPE opts into bf16
         kw.setdefault('dtype', dtype or self._knobs.get('dtype') or default_dtype())
         self._engine = ConvNetEngine(num_classes=num_classes, in_channels=channels, image_size=self.image_size,
@@ -83,10 +101,11 @@ class NativeImageClassifier(BaseModel):
         tm = self.timings = {}
         t_start = time.perf_counter()
         augment = self._augment()
+        regularisers = self._regularisers()
         images, labels, classes = self._load(dataset_uri)
         tm['load'] = time.perf_counter() - t_start
         channels = 1 if images.ndim == 3 else images.shape[-1]
-        self._build(max(classes, 2), channels, augment=augment)
+        self._build(max(classes, 2), channels, augment=augment, **regularisers)
         tm['build'] = time.perf_counter() - t_start - tm['load']
         eng = self._engine
         x_all = eng.prepare_inputs(images)
@@ -149,11 +168,14 @@ class NativeImageClassifier(BaseModel):
                 if hasattr(eng.opt, 'set_lr_scale') and sched == 'cosine':
                     eng.opt.set_lr_scale(0.5 * (1.0 + math.cos(math.pi * step / total)))
                 idx = perm[b * bs:(b + 1) * bs]
-                if augment is not None:
+                if eng.mix is not None:     # augments too, and leaves the partner labels and lam with the engine
+                    eng.mix_batch(x_all, y_all, idx, epoch, b, xb, yb)
+                elif augment is not None:
                     eng.augment_batch(x_all, idx, epoch, xb)
                 else:
                     torch.index_select(x_all, 0, idx, out=xb)
-                torch.index_select(y_all, 0, idx, out=yb)
+                if eng.mix is None:
+                    torch.index_select(y_all, 0, idx, out=yb)
                 if use_graph:
                     eng.step_graph(xb, yb)
                 else:

@@ -48,6 +48,20 @@ class VggSmallAug(VggSmall):
         return cfg
 
 
+class VggSmallReg(VggSmallAug):
+    """VggSmallAug with the soft-target regularisers in the search space: mixup or CutMix of every batch with
+    itself shifted by one row (``mix``; ``mix_alpha`` and ``mix_prob`` keep their defaults) and label smoothing —
+    mixed inside the step graph's prologue launch and scored by the soft-target loss kernels
+    (``ConvNetEngine(mix=..., label_smoothing=...)``)."""
+
+    @staticmethod
+    def get_knob_config():
+        cfg = VggSmallAug.get_knob_config()
+        cfg['mix'] = CategoricalKnob(['none', 'mixup', 'cutmix'])
+        cfg['label_smoothing'] = FloatKnob(0.0, 0.2)
+        return cfg
+
+
 class VggSmallTrial(VggSmall):
     """The benchmark's trial definition (bench.py phase 2): VggSmall at full width, batch 256, ten
     epochs over a CIFAR-sized train split (50k images), evaluated on 10k, parameters pickled — a

@@ -41,12 +41,15 @@ _SIGS = {
     "rk_gather_batch": [vp, i64, vp, vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, i32, i64, vp],
     "rk_gather_batch_aug": [vp, i64, vp, vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, i32, i64, i32, i32, i32, i32, f32,
                             C.c_ulonglong, C.c_uint, vp, vp],
+    "rk_gather_batch_mix": [vp, i64, vp, vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, i32, i64, i32, i32, i32, i32, i32,
+                            f32, C.c_ulonglong, C.c_uint, vp, i32, i32, vp, vp, vp, vp, vp],
     "rk_reduce_slabs_epi": [vp, i32, i32, i32, vp, i32, f32, f32, vp, vp, i32, vp],
     "rk_slab_epi": [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp],
     "rk_conv_wt": [vp, vp, vp, i32, vp, vp],
     "rk_bn_finalize_bwd": [vp, i32, i32, f64, vp, vp, vp, vp, vp, vp, i32, vp],
     "rk_bn_bwd_apply": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, vp],
     "rk_softmax_xent": [vp, i32, vp, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, vp],
+    "rk_softmax_xent_soft": [vp, i32, vp, vp, vp, f32, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp],
     "rk_sgd_step": [vp, vp, vp, vp, i64, f32, f32, f32, i32, f32, vp, i64, vp, vp],
     "rk_adam_step": [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, i32, f32, f32, f32, vp, vp, vp],
     "rk_add_int": [vp, i32, vp],
@@ -105,6 +108,7 @@ _SIGS = {
     "rk_bnf_eval_grp": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f32, vp],
     "rk_pack_nhwc_f32": [vp, i32, i32, i32, i32, i32, i32, f32, f32, vp, vp, i32, vp],
     "rk_softmax_xent_f32": [vp, i32, vp, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, vp],
+    "rk_softmax_xent_f32_soft": [vp, i32, vp, vp, vp, f32, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp],
     # table-driven gathers (PG-GAN up / down convs), resampling, fp32 PG-GAN side kernels
     "rk_sgemm_g": [i32, i32, i32, vp, vp, vp, vp] + [i32] * 14 + [u32p, u32p, C.c_uint, i32, i64, i32, i64, i32, f32,
                                                                  f32, i64, i64, vp],
@@ -125,6 +129,7 @@ _SIGS = {
     "rk_softmax_xent_f32s": [vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, vp],
     # fused classifier head (head.hip)
     "rk_head_fwd_bwd": [vp, i32, i32, vp, vp, i32, vp, i32, f32, vp, vp, i32, vp, vp, vp, vp],
+    "rk_head_fwd_bwd_soft": [vp, i32, i32, vp, vp, i32, vp, vp, vp, f32, i32, f32, vp, vp, i32, vp, vp, vp, vp],
     "rk_head_dw": [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp],
     # pre-split X6 GEMMs (x6p.hip) and their plane producers (winograd4.hip)
     "rk_x6p_gemm": [i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i32, i32, i32, i64,

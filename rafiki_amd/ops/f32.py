@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib, autotune
-from .functional import ACT_LRELU, ACT_NONE, ACT_RELU, bn_slots, cdiv  # noqa: F401
+from .functional import ACT_LRELU, ACT_NONE, ACT_RELU, _check_soft, bn_slots, cdiv  # noqa: F401
 
 KIND_CONV, KIND_WGRAD, KIND_DENSE, KIND_DENSE_DX, KIND_DENSE_DW = 0, 2, 3, 4, 5
 F_RELU, F_BIAS, F_STATS, F_GATE, F_ACCUM, F_LRELU, F_BNB, F_BNP = 1, 2, 4, 8, 16, 32, 512, 1024
@@ -1419,6 +1419,20 @@ def softmax_xent(logits, labels, ncls, *, dlogits=None, probs=None, loss_sum=Non
               _p(correct), _p(counted), _s())
 
 
+def softmax_xent_soft(logits, labels, ncls, *, labels2=None, lam=None, eps=0.0, dlogits=None, loss_sum=None,
+                      correct=None, counted=None, ignore_index=-100, grad_scale=None):
+    """``functional.softmax_xent_soft`` with fp32 d(logits)."""
+    B = logits.shape[0]
+    if grad_scale is None:
+        grad_scale = 1.0 / max(1, B)
+    if dlogits is not None:
+        _check(dlogits, 'softmax_xent_soft dlogits')
+    _check_soft(labels2, lam, labels)
+    _lib.call("rk_softmax_xent_f32_soft", _p(logits), logits.stride(0), _p(labels), _p(labels2), _p(lam), float(eps),
+              B, ncls, ignore_index, float(grad_scale), _p(dlogits), 0 if dlogits is None else dlogits.stride(0),
+              _p(loss_sum), _p(correct), _p(counted), _s())
+
+
 HEAD_NC = (8, 16, 32)
 
 
@@ -1438,6 +1452,19 @@ def head_fwd_bwd(z, w, bias, labels, ncls, *, dlogits, dz, gated, loss_sum=None,
     _lib.call("rk_head_fwd_bwd", _p(z), B, D, _p(w), _p(bias), NC, _p(labels), int(ncls),
               float(1.0 / max(1, B) if grad_scale is None else grad_scale), _p(dlogits), _p(dz), int(bool(gated)),
               _p(loss_sum), _p(correct), _p(counted), _s())
+
+
+def head_fwd_bwd_soft(z, w, bias, labels, ncls, *, labels2=None, lam=None, eps=0.0, dlogits, dz, gated,
+                      loss_sum=None, correct=None, counted=None, grad_scale=None):
+    """``head_fwd_bwd`` against the soft target of ``softmax_xent_soft`` (labels2 / lam / eps as there)."""
+    _check(z, 'head z')
+    B, D = z.shape
+    NC = w.shape[0]
+    assert w.shape == (NC, D) and dlogits.shape == (B, NC) and dz.shape == (B, D)
+    _check_soft(labels2, lam, labels)
+    _lib.call("rk_head_fwd_bwd_soft", _p(z), B, D, _p(w), _p(bias), NC, _p(labels), _p(labels2), _p(lam), float(eps),
+              int(ncls), float(1.0 / max(1, B) if grad_scale is None else grad_scale), _p(dlogits), _p(dz),
+              int(bool(gated)), _p(loss_sum), _p(correct), _p(counted), _s())
 
 
 def head_dw(z, dlogits, dz, *, dw, db=None, dbh=None):

@@ -708,6 +708,30 @@ def softmax_xent(logits, labels, ncls, *, dlogits=None, probs=None, loss_sum=Non
               _p(counted), _s())
 
 
+def _check_soft(labels2, lam, labels):
+    """Argument checks shared by the soft-target loss wrappers (both dtypes and the fused head); the launchers
+    themselves refuse an eps outside [0, 1)."""
+    if labels2 is not None and (labels2.dtype != torch.int32 or labels2.shape != labels.shape):
+        raise ValueError('labels2 must be int32 of the shape of labels')
+    if lam is not None and (lam.dtype != torch.float32 or lam.device != labels.device or lam.numel() < 1):
+        raise ValueError('lam must be a device float32 tensor')
+
+
+def softmax_xent_soft(logits, labels, ncls, *, labels2=None, lam=None, eps=0.0, dlogits=None, loss_sum=None,
+                      correct=None, counted=None, ignore_index=-100, grad_scale=None):
+    """``softmax_xent`` against the soft target t = (1 - eps) * (lam * onehot(labels) + (1 - lam) *
+    onehot(labels2)) + eps / ncls: dlogits = (softmax - t) * grad_scale.  ``labels2`` None: smoothing only;
+    ``lam`` a device float32 [1] (None: 1).  A row counts only if both of its labels are valid, and as correct
+    when the argmax is the label with the larger share (labels when lam >= 0.5)."""
+    B = logits.shape[0]
+    if grad_scale is None:
+        grad_scale = 1.0 / max(1, B)
+    _check_soft(labels2, lam, labels)
+    _lib.call("rk_softmax_xent_soft", _p(logits), logits.stride(0), _p(labels), _p(labels2), _p(lam), float(eps), B,
+              ncls, ignore_index, float(grad_scale), _p(dlogits), 0 if dlogits is None else dlogits.stride(0),
+              _p(loss_sum), _p(correct), _p(counted), _s())
+
+
 def sgd_step(w, g, mom=None, *, wb=None, lr, momentum=0.0, weight_decay=0.0, nesterov=False, grad_scale=1.0,
              lr_tensor=None, decay_end=None, bump=None):
     """Fused SGD over a flat range; ``weight_decay`` applies to elements [0, decay_end) (default: all).
@@ -921,6 +945,52 @@ def gather_batch_aug(data, labels, sched, counter, out_x, out_y, *, pad, flip_p,
               _p(zero), 0 if zero is None else zero.numel(), _p(done), _p(lr_table), _p(lr_out), sched.shape[0],
               data.shape[0], H, W, pixel_bytes // 16, int(pad), float(flip_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
               int(stream_id) & 0xFFFFFFFF, _p(epoch), _s())
+    return out_x
+
+
+def gather_batch_mix(data, labels, sched, counter, out_x, out_y, *, kind, lam_table, box_table, out_y2, lam_out,
+                     pad=None, flip_p=0.0, seed=0, stream_id=0, epoch=None, zero=None, done=None, lr_table=None,
+                     lr_out=None):
+    """``gather_batch`` (``pad`` None) or ``gather_batch_aug`` that mixes every output row b with its partner, the
+    row of sched[*counter][(b + 1) % B], in the same launch: ``kind`` 'mixup' blends lam * a + (1 - lam) * p in
+    fp32, 'cutmix' copies p inside the box (y0, y1, x0, x1) and a outside, with lam = lam_table[*counter] (fp32
+    [steps]) and the box = box_table[*counter] (int32 [steps, 4], clamped to the image by the kernel).  out_y /
+    out_y2 take the two labels and lam_out[0] the step's lam, for the soft-target loss later in the step.
+    ``rafiki_amd.ops.mix`` is the host twin."""
+    from .mix import MODE
+    B = out_x.shape[0]
+    if kind not in MODE:
+        raise ValueError('gather_batch_mix: kind must be one of {}, got {!r}'.format(tuple(MODE), kind))
+    if data.dim() != 4:
+        raise ValueError('gather_batch_mix: data must be NHWC [N, H, W, C], got {}'.format(tuple(data.shape)))
+    if data.dtype not in (torch.float32, torch.bfloat16) or out_x.dtype != data.dtype:
+        raise ValueError('gather_batch_mix: data and out_x must both be float32 or bfloat16')
+    H, W = int(data.shape[1]), int(data.shape[2])
+    row_bytes = data[0].numel() * data.element_size()
+    pixel_bytes = data.shape[3] * data.element_size()   # not a multiple of 16: the kernel refuses the row size
+    steps = sched.shape[0] if sched.dim() == 2 else 0
+    if zero is not None:
+        assert zero.dtype == torch.float64 and zero.is_contiguous()
+    if sched.dim() != 2 or sched.shape[1] != B or sched.dtype != torch.int64:
+        raise ValueError('sched must be int64 [steps, {}], got {} {}'.format(B, sched.dtype, tuple(sched.shape)))
+    if lr_table is not None and lr_table.numel() < steps:
+        raise ValueError('lr_table shorter than the schedule')
+    if epoch is not None and (epoch.dtype != torch.int32 or epoch.device != data.device):
+        raise ValueError('epoch must be a device int32 tensor')
+    if lam_table is not None and (lam_table.dtype != torch.float32 or lam_table.numel() < steps):
+        raise ValueError('lam_table must be float32 and no shorter than the schedule')
+    if box_table is not None and (box_table.dtype != torch.int32 or box_table.numel() < 4 * steps or
+                                  not box_table.is_contiguous()):
+        raise ValueError('box_table must be contiguous int32 [steps, 4] and no shorter than the schedule')
+    if out_y2 is not None and (out_y2.dtype != torch.int32 or out_y2.numel() < B):
+        raise ValueError('out_y2 must be int32 [{}]'.format(B))
+    if lam_out is not None and lam_out.dtype != torch.float32:
+        raise ValueError('lam_out must be float32')
+    _lib.call("rk_gather_batch_mix", _p(data), row_bytes, _p(labels), _p(sched), _p(counter), B, _p(out_x), _p(out_y),
+              _p(zero), 0 if zero is None else zero.numel(), _p(done), _p(lr_table), _p(lr_out), steps,
+              data.shape[0], H, W, pixel_bytes // 16, int(pad is not None), int(pad or 0), float(flip_p),
+              int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id) & 0xFFFFFFFF, _p(epoch), MODE[kind],
+              int(data.dtype == torch.bfloat16), _p(lam_table), _p(box_table), _p(out_y2), _p(lam_out), _s())
     return out_x
 
 
