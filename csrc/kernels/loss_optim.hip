@@ -864,7 +864,7 @@ extern "C" int rk_reduce_slabs_epi(const float* slab, int S, int M, int N, const
 // out[m][n] (bf16) = sum_s slab[s][m][n] with the igemm tile epilogue's BatchNorm options, so the
 // small-M convs (VGG 4x4 / 8x8 layers: 64-128 output tiles of 128x128) can split K over the chip:
 //   mode 0 plain; mode 1 forward statistics (sum v, sum v^2) -> fp64 slot table acc [SL][2][N];
-//   mode 2 FLAG_BNB data-gradient: v *= [y*scale + shift > 0], (sum v, sum v*y) -> acc;
+//   mode 2 FLAG_BNB data-gradient: v *= [y*scale + shift > 0], (sum v, sum v*y) of the bf16 v as stored -> acc;
 //   mode 3 ReLU-backward gate: v *= [gate > 0].
 // A block sweeps whole rows: N/4 threads per row (4 fixed channels each), 256/(N/4) rows per sweep,
 // so a thread's channel sums stay in registers; one LDS fold per block, then one fp64 atomic per
@@ -921,7 +921,8 @@ __global__ __launch_bounds__(256) void slab_epi_kernel(const float* __restrict__
           if (mode == 3) {
             a[e] = yv > 0.f ? a[e] : 0.f;
           } else {
-            a[e] = yv * sc[e] + sh[e] > 0.f ? a[e] : 0.f;
+            // as FLAG_BNB: the sums see the bf16 value that is stored and that the BN-backward apply reads
+            a[e] = yv * sc[e] + sh[e] > 0.f ? (float)(bf16)a[e] : 0.f;
             s[e] += a[e];
             q[e] += a[e] * yv;
           }
