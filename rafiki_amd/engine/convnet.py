@@ -122,7 +122,8 @@ class ConvNetEngine:
                  bn_eps: float = 1e-5, bn_momentum: float = 0.1, optimizer: str = 'sgd', lr: float = 0.05,
                  momentum: float = 0.9, weight_decay: float = 5e-4, nesterov: bool = True,
                  betas=(0.9, 0.999), input_bn: bool = False, dtype: Optional[str] = None, bn: bool = True,
-                 augment: Optional[dict] = None, mix: Optional[dict] = None, label_smoothing: float = 0.0):
+                 augment: Optional[dict] = None, mix: Optional[dict] = None, label_smoothing: float = 0.0,
+                 dropout: float = 0.0, feature_dropout: float = 0.0):
         self.device = torch.device(device)
         self.dtype = dtype or default_dtype()
         if self.dtype not in DTYPES:
@@ -177,6 +178,21 @@ class ConvNetEngine:
         if not 0.0 <= self.label_smoothing < 1.0:
             raise ValueError('label_smoothing must lie in [0, 1), got {!r}'.format(label_smoothing))
         self.soft = self.mix is not None or self.label_smoothing > 0.0
+        # dropout: every FC hidden layer's output (after its ReLU) is dropped at this rate; feature_dropout: the
+        # flattened conv features that feed the first FC (or the output) layer.  In place, by ops dropout_ straight
+        # after the tensor is produced and again on the gradient that arrives at it; the multipliers are a function
+        # of (seed, site, epoch, step within the epoch), never stored (ops/dropout.py is the host twin).  Rate 0
+        # adds no launch and no buffer
+        self.dropout, self.feature_dropout = float(dropout), float(feature_dropout)
+        for k, v in (('dropout', self.dropout), ('feature_dropout', self.feature_dropout)):
+            if not 0.0 <= v < 1.0:
+                raise ValueError('{} must lie in [0, 1), got {!r}'.format(k, v))
+        if self.feature_dropout > 0.0 and self.flat_input:
+            raise ValueError('feature_dropout needs conv features; a flat-input net reads the caller\'s buffer')
+        self._drops = self.dropout > 0.0 or self.feature_dropout > 0.0
+        self._drop_at = [0, 0]                        # (epoch, step within it) of the next step: the CPU path
+        self._drop_step = self._drop_step_src = None  # device step word; the scheduled graph reads _ctr instead
+        self._dropped = {}                            # keep_dropped: site -> the tensor last dropped in the forward
         self._static_y2 = self._lam = self._lam_table = self._box_table = None
         # any image size: power-of-two maps use the shift-decoded (and LDS-DMA) gather, others the
         # reciprocal-decoded register-staged gather (VGG16 at 48x48: 48/24/12/6/3)
@@ -311,6 +327,10 @@ class ConvNetEngine:
     dgrad_wt = True
     # fp32 path: the classifier head (output layer, softmax-xent, its gradients) as two fused launches
     fused_head = True
+    # debug hook, off in every product path: the forward keeps a reference to each tensor it dropped (_dropped),
+    # which pins those activations — inside a captured step, blocks of the graph's private pool — for the
+    # engine's life.  The tests that compare a replay's zero pattern with the oracle's mask switch it on
+    keep_dropped = False
 
     def reset_metrics(self):
         self.loss_sum.zero_()
@@ -357,10 +377,14 @@ class ConvNetEngine:
             h = F.bn_act_fwd(raw, coeffs[2], coeffs[3], pool=False, act=F.ACT_NONE)
             in_saved = (raw, coeffs)
         feat = h.reshape(B, self.feat_dim)
+        if self.feature_dropout > 0.0:
+            self._drop(feat, -1, self.feature_dropout, forward=True)   # the last block's output: no kernel rereads it
         fc_in = [feat]
         z = feat
-        for (name, di, do, _) in self.fcs:
+        for k, (name, di, do, _) in enumerate(self.fcs):
             z = F.linear(z, fl.wb(name + '.w'), fl.w(name + '.b'), act=F.ACT_RELU)
+            if self.dropout > 0.0:
+                self._drop(z, k, self.dropout, forward=True)
             fc_in.append(z)
         logits = F.linear(z, fl.wb('out.w'), fl.w('out.b'), out_dtype=torch.float32)
         dlogits = torch.empty((B, self.ncls_p), dtype=torch.bfloat16, device=self.device)
@@ -378,12 +402,18 @@ class ConvNetEngine:
         for k in range(len(self.fcs) - 1, -1, -1):
             name = self.fcs[k][0]
             d = F.linear_dx(d, fl.wb(wname + '.w'), gate=fc_in[k + 1])
+            if self.dropout > 0.0:
+                # the gate tested the post-dropout activation, so dropped units are already zero; this supplies
+                # the 1 / (1 - p) still owed (the mask is idempotent)
+                self._drop(d, k, self.dropout)
             F.linear_dw(d, fc_in[k], out=fl.g(name + '.w'))
             F.colsum(d, fl.g(name + '.b'))
             wname = name
         if not self.blocks and not self.input_bn:
             return
         d = F.linear_dx(d, fl.wb(wname + '.w'))
+        if self.feature_dropout > 0.0:
+            self._drop(d, -1, self.feature_dropout)
         if self.input_bn:
             raw, coeffs = in_saved
             F.bn_bwd(d.view(B, 1, 1, self.feat_dim), raw, coeffs, fl.w('in_bn.gamma'), pool=False, act=F.ACT_NONE,
@@ -487,10 +517,17 @@ class ConvNetEngine:
                                  self.bn_momentum, pool=False, act=F.ACT_NONE)
             in_saved = (raw, coeffs)
         feat = h.reshape(B, self.feat_dim)
+        if self.feature_dropout > 0.0:
+            # in place on the last block's output.  The backward pass rereads it only in a bn=False block without
+            # a pool, whose saved post-ReLU output doubles as its ReLU mask: a kept value keeps its sign, and a
+            # dropped one becomes a masked one, where the gradient is zero anyway
+            self._drop(feat, -1, self.feature_dropout, forward=True)
         fc_in = [feat]
         z = feat
-        for (name, di, do, _) in self.fcs:
+        for k, (name, di, do, _) in enumerate(self.fcs):
             z = S.linear(z, fl.w(name + '.w'), fl.w(name + '.b'), act=F.ACT_RELU)
+            if self.dropout > 0.0:
+                self._drop(z, k, self.dropout, forward=True)
             fc_in.append(z)
         dlogits = torch.empty((B, self.ncls_p), dtype=torch.float32, device=self.device)
         k_top = len(self.fcs) - 1
@@ -506,6 +543,13 @@ class ConvNetEngine:
             else:
                 S.head_fwd_bwd(z, fl.w('out.w'), fl.w('out.b'), labels, self.num_classes, dlogits=dlogits, dz=dz,
                                gated=gated, loss_sum=self.loss_sum, correct=self.correct, counted=self.seen)
+            # dz arrives at a dropped tensor: the top hidden layer's output (its gate already zeroed the dropped
+            # units, the 1 / (1 - p) is still owed) or, with no hidden layer, the features.  Before head_dw, so
+            # dbh and the linear_dw below see the scaled gradient
+            if gated and self.dropout > 0.0:
+                self._drop(dz, k_top, self.dropout)
+            elif not gated and self.feature_dropout > 0.0:
+                self._drop(dz, -1, self.feature_dropout)
             S.head_dw(z, dlogits, dz, dw=fl.g('out.w'), db=fl.g('out.b'),
                       dbh=fl.g(self.fcs[k_top][0] + '.b') if gated else None)
             d = dz
@@ -529,6 +573,8 @@ class ConvNetEngine:
         for k in range(k_top, -1, -1):
             name = self.fcs[k][0]
             d = S.linear_dx(d, fl.w(wname + '.w'), gate=fc_in[k + 1])
+            if self.dropout > 0.0:
+                self._drop(d, k, self.dropout)   # gated above; the 1 / (1 - p) is still owed
             S.linear_dw(d, fc_in[k], out=fl.g(name + '.w'))
             S.colsum(d, fl.g(name + '.b'))
             wname = name
@@ -536,6 +582,8 @@ class ConvNetEngine:
             return
         if wname is not None:
             d = S.linear_dx(d, fl.w(wname + '.w'))
+            if self.feature_dropout > 0.0:
+                self._drop(d, -1, self.feature_dropout)
         if self.input_bn:
             raw, coeffs = in_saved
             S.bn_bwd(d.view(B, 1, 1, self.feat_dim), raw, coeffs, fl.w('in_bn.gamma'), accs[-1][1], pool=False,
@@ -628,8 +676,12 @@ class ConvNetEngine:
     # ------------------------------------------------------------------------ reference path
     def reference_loss(self, x_nhwc: torch.Tensor, labels: torch.Tensor, params: Optional[dict] = None,
                        training=True, update_running=False, emulate_bf16=False, labels2=None, lam=None,
-                       smoothing=0.0):
+                       smoothing=0.0, drop=None):
         """Pure PyTorch fp32 forward of the same network (NCHW internally). Returns (loss, logits).
+
+        ``drop`` {site: multipliers}: the dropout multipliers (0 or 1 / (1 - p)) of the flattened NHWC features
+        [B, feat_dim] (site DROP_STREAM) and of FC hidden layer k's output [B, padded width] (site DROP_STREAM + 1
+        + k); a site that is absent, or None, drops nothing.
 
         ``labels2`` / ``lam`` / ``smoothing``: the soft target (1 - smoothing) * (lam * onehot(labels) +
         (1 - lam) * onehot(labels2)) + smoothing / num_classes; the defaults give the hard-label loss.
@@ -683,8 +735,14 @@ class ConvNetEngine:
                 h = rnd(h)
         else:
             h = h.permute(0, 2, 3, 1).reshape(h.shape[0], -1)
-        for (name, di, do, _) in self.fcs:
+        if drop:
+            from ..ops.dropout import DROP_STREAM
+            if drop.get(DROP_STREAM) is not None:
+                h = rnd(h * drop[DROP_STREAM].to(h))
+        for k, (name, di, do, _) in enumerate(self.fcs):
             h = rnd(torch.relu(h @ rndw(P[name + '.w']).t() + P[name + '.b']))
+            if drop and drop.get(DROP_STREAM + 1 + k) is not None:
+                h = rnd(h * drop[DROP_STREAM + 1 + k].to(h))
         logits = (h @ rndw(P['out.w']).t() + P['out.b'])[:, :self.num_classes]
         logits = _bf16_grad(logits) if emulate_bf16 and emulate_bf16 != 'fwd' else logits
         if labels is None:
@@ -710,6 +768,8 @@ class ConvNetEngine:
             soft = dict(labels2=sa['labels2'], lam=sa['lam'], smoothing=sa['eps'])
             if sa['labels2'] is not None and float(sa['lam']) < 0.5:
                 counts_for = sa['labels2']      # a prediction counts as correct for the label with the larger share
+        if self._drops:
+            soft['drop'] = self._drop_mults(x.shape[0], *self._drop_at)
         loss, logits = self.reference_loss(x, labels, params, training=True, update_running=True, **soft)
         grads = torch.autograd.grad(loss, [params[n] for n in fl.names()])
         for n, g in zip(fl.names(), grads):
@@ -785,6 +845,10 @@ class ConvNetEngine:
         # the step counter advances inside the step's last kernel (SGD) or, for other optimizers, in
         # the prologue once every gather block has read it
         opt_bumps = isinstance(self.opt, FlatSGD)
+        if self._drops and not opt_bumps:
+            # there the counter advances in the prologue, so the step's kernels would read the next row's word
+            raise NotImplementedError('dropout in the scheduled graph needs the SGD optimizer (the step counter '
+                                      'must advance in the step\'s last kernel); use capture + set_step')
 
         gather, aug = F.gather_batch, {}
         if self.mix is not None:
@@ -806,10 +870,13 @@ class ConvNetEngine:
             self._acc_zeroed_by_prologue = accs is not None
             if opt_bumps:
                 self.opt.bump = self._ctr
+            if self._drops:
+                self._drop_step_src = self._ctr   # forward and backward read it before the SGD kernel bumps it
             try:
                 self._train_step_gpu(self._static_x, self._static_y)
             finally:
                 self._acc_zeroed_by_prologue = False
+                self._drop_step_src = None
                 if opt_bumps:
                     self.opt.bump = None
 
@@ -838,13 +905,14 @@ class ConvNetEngine:
     def set_schedule(self, idx, start: int = 0, lr_scales=None, epoch=None):
         """idx: [steps, B] row indices (device) -> schedule buffer; the next replay uses row ``start``.
         ``lr_scales`` [steps] (optional): the optimizer's LR multiplier of each step.  ``epoch`` (optional, an
-        augmenting engine): the epoch the replays draw their crops and mirrors for."""
+        augmenting or dropping engine): the epoch the replays draw their crops, mirrors and dropout multipliers
+        for."""
         self._sched[:idx.shape[0]].copy_(idx)
         self._ctr.fill_(start)
         if lr_scales is not None:
             self._lr_table[:len(lr_scales)].copy_(torch.as_tensor(lr_scales, dtype=torch.float32))
-        if epoch is not None and self.augment is not None:
-            self._aug_epoch.fill_(int(epoch))
+        if epoch is not None and (self.augment is not None or self._drops):
+            self._epoch_word().fill_(int(epoch))
         if epoch is not None and self.mix is not None:
             lam, box = self._mix_plan(epoch, idx.shape[0])
             self._lam_table[:idx.shape[0]].copy_(torch.from_numpy(lam[:idx.shape[0]]))
@@ -916,12 +984,60 @@ class ConvNetEngine:
         self._lam.fill_(lam)
         return out_x
 
-    def _aug_args(self):
-        """The augmentation arguments of F.gather_batch_aug; the device epoch word is made on first use."""
-        from ..ops.augment import AUG_STREAM
+    # ----------------------------------------------------------------------------- dropout
+    def set_step(self, epoch, step_in_epoch):
+        """The identity (epoch, step within it) of the next step, for the loops that feed the step themselves
+        (``capture`` + ``step_graph``, ``train_step``, ``forward_backward``): dropout draws its multipliers for it.
+        Two device words on the GPU (a captured step reads them at replay time), two host ints on the CPU.  The
+        scheduled graph needs no call: it reads its own step counter and ``set_schedule``'s epoch."""
+        self._drop_at = [int(epoch), int(step_in_epoch)]
+        if self._drops and self.device.type == 'cuda':
+            self._drop_words()
+            self._aug_epoch.fill_(int(epoch))
+            self._drop_step.fill_(int(step_in_epoch))
+
+    def _epoch_word(self):
+        """The device epoch word the augmentation and dropout draws share, made on first use."""
         if self._aug_epoch is None:
             self._aug_epoch = torch.zeros(1, dtype=torch.int32, device=self.device)
             self._aug_ctr0 = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return self._aug_epoch
+
+    def _drop_words(self):
+        """(step word, epoch word) a dropout launch reads: inside the scheduled graph the step word is the graph's
+        own counter (``_drop_step_src``), elsewhere the one ``set_step`` fills."""
+        if self._drop_step is None:
+            self._drop_step = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return (self._drop_step if self._drop_step_src is None else self._drop_step_src), self._epoch_word()
+
+    def _drop(self, t, k, p, forward=False):
+        """Drop ``t`` in place at rate ``p``: k = -1 the flattened features (site DROP_STREAM), k >= 0 FC hidden
+        layer k (site DROP_STREAM + 1 + k).  The same call serves the activation and its gradient."""
+        from ..ops.dropout import DROP_STREAM
+        step, epoch = self._drop_words()
+        F.dropout_(t, p, seed=self._aug_seed, site=DROP_STREAM + 1 + k, step=step, epoch=epoch)
+        if forward and self.keep_dropped:
+            self._dropped[DROP_STREAM + 1 + k] = t
+        return t
+
+    def _drop_mults(self, B, epoch, step):
+        """site -> fp32 multipliers of each dropped tensor of a batch of ``B`` rows at (epoch, step), from the host
+        twin: the ``drop`` argument of ``reference_loss``."""
+        from ..ops import dropout as D
+        out = {}
+        if self.feature_dropout > 0.0:
+            out[D.DROP_STREAM] = D.multipliers(self._aug_seed, D.DROP_STREAM, epoch, step, (B, self.feat_dim),
+                                               self.feature_dropout)
+        if self.dropout > 0.0:
+            for k, (_, _, dp, _) in enumerate(self.fcs):
+                out[D.DROP_STREAM + 1 + k] = D.multipliers(self._aug_seed, D.DROP_STREAM + 1 + k, epoch, step,
+                                                           (B, dp), self.dropout)
+        return out
+
+    def _aug_args(self):
+        """The augmentation arguments of F.gather_batch_aug; the device epoch word is made on first use."""
+        from ..ops.augment import AUG_STREAM
+        self._epoch_word()
         return dict(pad=self.augment['pad'], flip_p=self.augment['flip'], seed=self._aug_seed,
                     stream_id=AUG_STREAM, epoch=self._aug_epoch)
 
@@ -1126,9 +1242,11 @@ class ConvNetEngine:
         from ..ops.graphs import quiesced
         with quiesced():
             for a in ('_graph', '_sched_graph', '_static_x', '_static_y', '_sched', '_ctr', '_ww', '_wt',
-                      '_static_y2', '_lam', '_lam_table', '_box_table', '_mb_lam', '_mb_box'):
+                      '_static_y2', '_lam', '_lam_table', '_box_table', '_mb_lam', '_mb_box',
+                      '_drop_step'):
                 if hasattr(self, a):
                     setattr(self, a, None)
+            self._dropped = {}
             self.opt = None
 
     # ---------------------------------------------------------------------------- state I/O

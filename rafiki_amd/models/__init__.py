@@ -3,7 +3,8 @@
   VggSmall (vgg_small.py)        gfx950 engine, the BASELINE benchmark architecture
   VggSmallAug (vgg_small.py)     VggSmall with the crop / mirror augmentation in the search space
   VggSmallReg (vgg_small.py)     VggSmallAug with mixup / CutMix and label smoothing in the search space
-  Vgg16 (vgg16.py)               gfx950 engine, TfVgg16 semantics (48x48x3, Adam)
+  VggSmallDrop (vgg_small.py)    VggSmallReg with dropout (FC hidden layers, conv features) in the search space
+  Vgg16 (vgg16.py)          gfx950 engine, TfVgg16 semantics (48x48x3, Adam)
   FeedForward (feed_forward.py)  gfx950 engine, TfFeedForward semantics
   SkDt, SkSvm (sk_models.py)     scikit-learn on CPU
   BigramHmm, PyBiLstm (pos_tagging.py)
@@ -16,6 +17,7 @@ ZOO = {
     'VggSmall': ('vgg_small.py', 'IMAGE_CLASSIFICATION'),
     'VggSmallAug': ('vgg_small.py', 'IMAGE_CLASSIFICATION'),
     'VggSmallReg': ('vgg_small.py', 'IMAGE_CLASSIFICATION'),
+    'VggSmallDrop': ('vgg_small.py', 'IMAGE_CLASSIFICATION'),
     'VggSmallTrial': ('vgg_small.py', 'IMAGE_CLASSIFICATION'),
     'VggSmallProbe': ('vgg_small.py', 'IMAGE_CLASSIFICATION'),
     'Vgg16': ('vgg16.py', 'IMAGE_CLASSIFICATION'),

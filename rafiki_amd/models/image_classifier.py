@@ -72,7 +72,9 @@ class NativeImageClassifier(BaseModel):
     def _regularisers(self):
         """The engine's ``mix`` and ``label_smoothing`` arguments from the knobs ``mix`` (one of MIX_MODES, default
         'none'), ``mix_alpha`` (the Beta parameter, default 1.0), ``mix_prob`` (the share of mixed steps, default 1.0
-        for mixup and 0.5 for cutmix) and ``label_smoothing`` (default 0.0).  Training only."""
+        for mixup and 0.5 for cutmix) and ``label_smoothing`` (default 0.0); and its ``dropout`` (every FC hidden
+        layer's output) and ``feature_dropout`` (the flattened conv features) rates from the knobs of those names
+        (default 0.0, each in [0, 1)), passed on only when non-zero.  Training only."""
         mode = self._knobs.get('mix', 'none')
         if mode not in self.MIX_MODES:
             raise ValueError('mix must be one of {}, got {!r}'.format(self.MIX_MODES, mode))
@@ -82,6 +84,12 @@ class NativeImageClassifier(BaseModel):
                           'prob': float(self._knobs.get('mix_prob', 1.0 if mode == 'mixup' else 0.5))}
         if float(self._knobs.get('label_smoothing', 0.0)) != 0.0:
             out['label_smoothing'] = float(self._knobs['label_smoothing'])
+        for name in ('dropout', 'feature_dropout'):
+            rate = float(self._knobs.get(name, 0.0))
+            if not 0.0 <= rate < 1.0:
+                raise ValueError('{} must lie in [0, 1), got {!r}'.format(name, self._knobs[name]))
+            if rate != 0.0:
+                out[name] = rate
         return out
 
     def _build(self, num_classes, channels, dtype=None, augment=None, **regularisers):
@@ -176,6 +184,9 @@ class NativeImageClassifier(BaseModel):
                     torch.index_select(x_all, 0, idx, out=xb)
                 if eng.mix is None:
                     torch.index_select(y_all, 0, idx, out=yb)
+                if eng.dropout > 0.0 or eng.feature_dropout > 0.0:
+                    eng.set_step(epoch, b)   # the multipliers are drawn per (seed, epoch, step): a resumed trial
+                    # continues the stream
                 if use_graph:
                     eng.step_graph(xb, yb)
                 else:

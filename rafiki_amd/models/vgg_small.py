@@ -62,6 +62,19 @@ class VggSmallReg(VggSmallAug):
         return cfg
 
 
+class VggSmallDrop(VggSmallReg):
+    """VggSmallReg with dropout in the search space: ``dropout`` on the FC hidden layer's output and
+    ``feature_dropout`` on the flattened conv features, drawn per (seed, epoch, step) by an in-place kernel inside
+    the step graph and again on the arriving gradients (``ConvNetEngine(dropout=..., feature_dropout=...)``)."""
+
+    @staticmethod
+    def get_knob_config():
+        cfg = VggSmallReg.get_knob_config()
+        cfg['dropout'] = FloatKnob(0.0, 0.5)
+        cfg['feature_dropout'] = FloatKnob(0.0, 0.3)
+        return cfg
+
+
 class VggSmallTrial(VggSmall):
     """The benchmark's trial definition (bench.py phase 2): VggSmall at full width, batch 256, ten
     epochs over a CIFAR-sized train split (50k images), evaluated on 10k, parameters pickled — a

@@ -131,6 +131,8 @@ _SIGS = {
     "rk_head_fwd_bwd": [vp, i32, i32, vp, vp, i32, vp, i32, f32, vp, vp, i32, vp, vp, vp, vp],
     "rk_head_fwd_bwd_soft": [vp, i32, i32, vp, vp, i32, vp, vp, vp, f32, i32, f32, vp, vp, i32, vp, vp, vp, vp],
     "rk_head_dw": [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp],
+    # in-place dropout of the conv-net step, multipliers regenerated in the backward pass (dropout.hip)
+    "rk_dropout": [vp, i64, i32, f32, C.c_ulonglong, C.c_uint, vp, vp, vp],
     # pre-split X6 GEMMs (x6p.hip) and their plane producers (winograd4.hip)
     "rk_x6p_gemm": [i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, i64, i32, i32, i32, i64,
                     i64, i64, vp],

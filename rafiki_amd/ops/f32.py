@@ -21,7 +21,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib, autotune
-from .functional import ACT_LRELU, ACT_NONE, ACT_RELU, _check_soft, bn_slots, cdiv  # noqa: F401
+from .functional import ACT_LRELU, ACT_NONE, ACT_RELU, _check_soft, bn_slots, cdiv, dropout_  # noqa: F401
 
 KIND_CONV, KIND_WGRAD, KIND_DENSE, KIND_DENSE_DX, KIND_DENSE_DW = 0, 2, 3, 4, 5
 F_RELU, F_BIAS, F_STATS, F_GATE, F_ACCUM, F_LRELU, F_BNB, F_BNP = 1, 2, 4, 8, 16, 32, 512, 1024

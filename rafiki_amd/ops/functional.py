@@ -1026,6 +1026,23 @@ def philox_(out, dist, *, seed, stream_id, step=None, hi=0, a=0.0, b=1.0):
     return out
 
 
+def dropout_(x, p, *, seed, site, step=None, epoch=None):
+    """x (contiguous fp32 or bf16) *= its inverted-dropout multipliers, in place: element i is kept iff
+    u01(word i % 4 of Philox4x32-10 at counter (i / 4, site, *step, *epoch), key seed) >= p and scaled by the fp32
+    1 / (1 - p), else written as zero.  ``step`` / ``epoch`` are device int32 words (None: 0) read by the kernel, so
+    a replayed graph draws for what they hold then.  The same call on the gradient that arrives at ``x`` is the
+    backward pass (nothing is stored).  ``rafiki_amd.ops.dropout`` is the host twin."""
+    if x.dtype not in (torch.float32, torch.bfloat16) or not x.is_contiguous():
+        raise ValueError('dropout_: x must be contiguous float32 or bfloat16, got {} {}'.format(
+            x.dtype, tuple(x.shape)))
+    for name, t in (('step', step), ('epoch', epoch)):
+        if t is not None and (t.dtype != torch.int32 or t.device != x.device or t.numel() < 1):
+            raise ValueError('dropout_: {} must be a device int32 tensor'.format(name))
+    _lib.call("rk_dropout", _p(x), x.numel(), int(x.dtype == torch.bfloat16), float(p),
+              int(seed) & 0xFFFFFFFFFFFFFFFF, int(site) & 0xFFFFFFFF, _p(step), _p(epoch), _s())
+    return x
+
+
 def lrelu_pixelnorm(x, bias=None, *, slope=0.2, eps=1e-8, dz=None, out=None):
     """z = PN(lrelu(x + bias)) over the last (channel) dim of bf16 or fp32 NHWC rows; with ``dz`` the
     backward dL/dx instead (recomputes the activation from x)."""
