@@ -168,6 +168,10 @@ def lib():
             raise NativeLibraryError(
                 f"{KERNEL_LIB} is missing: build it with `python -m rafiki_amd._build` "
                 "(the GPU path has no PyTorch fallback)")
+        # torch first: its wheel carries a HIP runtime of its own, and the streams and pointers the kernels get
+        # come from that one.  Loaded before torch, this library binds to the system runtime instead and every
+        # launch on a torch stream answers RK_ELAUNCH (`python __graft_entry__.py smoke` did).
+        import torch  # noqa: F401
         h = C.CDLL(str(KERNEL_LIB))
         for name, args in _SIGS.items():
             try:
