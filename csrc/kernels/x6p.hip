@@ -566,10 +566,10 @@ extern "C" int rk_x6p_split(const float* src, void* dst, int rows, int cols, int
 }
 
 // planes [3][cols][ldd] (plane stride ps) of the transpose of an fp32 [rows][lds] matrix; plane columns
-// rows .. ldd-1 zero; ldd % 4 == 0
+// rows .. ldd-1 zero; ldd % 4 == 0 and ps % 4 == 0 (the 8-B stores of every plane are aligned)
 extern "C" int rk_x6p_split_t(const float* src, void* dst, int rows, int cols, int lds, int ldd, long long ps,
                               void* stream) {
-  if (rows <= 0 || cols <= 0 || lds < cols || ldd < rows || (ldd & 3) || ps < (long long)cols * ldd)
+  if (rows <= 0 || cols <= 0 || lds < cols || ldd < rows || (ldd & 3) || (ps & 3) || ps < (long long)cols * ldd)
     return RK_EBADARG;
   const dim3 grid((unsigned)rk_cdiv(cols, 64), (unsigned)rk_cdiv(ldd, 64));
   hipLaunchKernelGGL(x6p_split_t_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, (bf16*)dst, rows, cols, lds,
