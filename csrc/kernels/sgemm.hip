@@ -414,20 +414,14 @@ int s_launch(const SgParams& p, int nst, int splits, hipStream_t st, bool x6) {
   constexpr int BM = WGM * 32 * MI, BN = WGN * 32 * NI;
   const int tiles = rk_cdiv(p.M, BM) * rk_cdiv(p.N, BN);
   dim3 grid(tiles * splits * ((GRP || AM == SM_KIN_CONVG) ? p.groups : 1));
-  if (nst == 3) {
-    if constexpr (WGM * WGN == 4) {  // 3-stage rings only for the 4-wave tiles (8-wave ones fill LDS at 2)
-      if (x6)
-        hipLaunchKernelGGL((sgemm_kernel<WGM, WGN, MI, NI, AM, BMD, 3, GRP, true>), grid, dim3(64 * WGM * WGN), 0, st, p);
-      else
-        hipLaunchKernelGGL((sgemm_kernel<WGM, WGN, MI, NI, AM, BMD, 3, GRP>), grid, dim3(64 * WGM * WGN), 0, st, p);
-    } else {
-      return RK_EUNSUPPORTED;
-    }
-  } else if (x6) {
-    hipLaunchKernelGGL((sgemm_kernel<WGM, WGN, MI, NI, AM, BMD, 2, GRP, true>), grid, dim3(64 * WGM * WGN), 0, st, p);
-  } else {
-    hipLaunchKernelGGL((sgemm_kernel<WGM, WGN, MI, NI, AM, BMD, 2, GRP>), grid, dim3(64 * WGM * WGN), 0, st, p);
-  }
+  // 3-stage rings only for the 4-wave tiles (8-wave ones fill LDS at 2): the others have no deep kernel
+  constexpr int DEEP = WGM * WGN == 4 ? 3 : 2;
+  if (nst == 3 && DEEP != 3) return RK_EUNSUPPORTED;
+  // [2-stage ring][f32 K loop], deep and X6 first: the order the kernels are instantiated in
+  static constexpr void (*kernels[2][2])(SgParams) = {
+      {sgemm_kernel<WGM, WGN, MI, NI, AM, BMD, DEEP, GRP, true>, sgemm_kernel<WGM, WGN, MI, NI, AM, BMD, DEEP, GRP>},
+      {sgemm_kernel<WGM, WGN, MI, NI, AM, BMD, 2, GRP, true>, sgemm_kernel<WGM, WGN, MI, NI, AM, BMD, 2, GRP>}};
+  hipLaunchKernelGGL(kernels[nst != 3][!x6], grid, dim3(64 * WGM * WGN), 0, st, p);
   RK_LAUNCH_CHECK();
   return RK_OK;
 }
@@ -460,6 +454,50 @@ int s_launch_tile(int tile, const SgParams& p, int nst, int splits, hipStream_t 
   return RK_EUNSUPPORTED;
 }
 
+// What the three entry points refuse alike, and first: operands outside one buffer descriptor, empty extents, an
+// unknown ring depth or tile code.  ``big``: tiles 4-7 exist (rk_sgemm only).
+int s_check(int tile, bool big, int nst, int M, int N, int K, int splits, long long bytesA, long long bytesB) {
+  if (bytesA <= 0 || bytesB <= 0 || bytesA >= (1ll << 31) || bytesB >= (1ll << 31)) return RK_EUNSUPPORTED;
+  const int t = tile & 15;
+  if (M <= 0 || N <= 0 || K <= 0 || splits <= 0 || (nst != 2 && nst != 3) || tile < 0 || t > 10 || tile > 26 ||
+      (!big && t > 3 && t < 8))
+    return RK_EBADARG;
+  return RK_OK;
+}
+// a gathered map: 16-B chunks of channels
+bool s_map_ok(int H, int W, int Cch) { return Cch % 4 == 0 && Cch > 0 && H > 0 && W > 0; }
+// split-K writes raw partial slabs: the epilogue belongs to the combine
+bool s_split_ok(int splits, int flags) {
+  return splits == 1 || !(flags & (SF_BIAS | SF_RELU | SF_LRELU | SF_GATE | SF_STATS | SF_BNB | SF_BNP));
+}
+// reciprocal decodes are exact below 2^22 (pixel indices, tap*C column indices)
+bool s_decode_exact(long long rows, int H, int W) { return rows + (long long)W * (H + 2) < (1ll << 22); }
+
+void s_row_grid(SgParams& p, int Ho, int Wo) {
+  p.Ho = Ho; p.Wo = Wo; p.log2Ho = rk_log2(Ho); p.log2Wo = rk_log2(Wo);
+  p.invHo = 1.0f / (float)Ho; p.invWo = 1.0f / (float)Wo;
+}
+
+// The argument block as every entry point fills it: operands, extents, the gathered H x W x Cch map with its
+// decode constants (the row grid = the map itself), the K split and the epilogue scalars; one group.
+SgParams s_params(const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int lda, int ldb,
+                  int ldc, int H, int W, int Cch, int taps, int splits, long long slabStride, int flags, float alpha,
+                  float slope, long long bytesA, long long bytesB) {
+  SgParams p{};
+  p.A = A; p.B = B; p.out = C; p.bias = bias;
+  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+  p.H = H; p.W = W; p.C = Cch; p.taps = taps;
+  p.log2H = rk_log2(H); p.log2W = rk_log2(W); p.log2C = rk_log2(Cch);
+  p.invC = 1.0f / (float)Cch; p.invH = 1.0f / (float)H; p.invW = 1.0f / (float)W;
+  s_row_grid(p, H, W);
+  p.ktPer = rk_cdiv(rk_cdiv(K, SBK), splits);
+  p.slabStride = splits > 1 ? slabStride : 0;
+  p.flags = flags; p.alpha = alpha; p.slope = slope;
+  p.bytesA = (unsigned long long)bytesA; p.bytesB = (unsigned long long)bytesB;
+  p.groups = 1;
+  return p;
+}
+
 }  // namespace
 
 // fp32 implicit GEMM.  kind: 0 conv forward (A = NHWC activation gathered per tap [M = pixels][K = taps*C],
@@ -475,10 +513,7 @@ extern "C" int rk_sgemm(int kind, int tile, int nst, const float* A, const float
                         double* stats, int slotMask, const float* gate, int M, int N, int K, int lda, int ldb,
                         int ldc, int H, int W, int Cch, int taps, int splits, long long slabStride, int flags,
                         float alpha, float slope, long long bytesA, long long bytesB, void* stream) {
-  if (bytesA <= 0 || bytesB <= 0 || bytesA >= (1ll << 31) || bytesB >= (1ll << 31)) return RK_EUNSUPPORTED;
-  if (M <= 0 || N <= 0 || K <= 0 || splits <= 0 || (nst != 2 && nst != 3) || tile < 0 || (tile & 15) > 10 ||
-      tile > 26)
-    return RK_EBADARG;
+  if (const int e = s_check(tile, true, nst, M, N, K, splits, bytesA, bytesB)) return e;
   if (taps != 1 && taps != 9) return RK_EBADARG;
   const bool conv = kind == 0 || kind == 2;
   // 16-B chunks: K-inner operands need K % 4 == 0 (and 16-B aligned rows); K-outer ones need the
@@ -489,26 +524,15 @@ extern "C" int rk_sgemm(int kind, int tile, int nst, const float* A, const float
   if ((kind == 0 || kind == 3) && ldb % 4) return RK_EUNSUPPORTED;
   if ((kind == 4 || kind == 5 || kind == 2) && (N % 4 || ldb % 4)) return RK_EUNSUPPORTED;
   if ((kind == 5 || kind == 2) && (M % 4 || lda % 4)) return RK_EUNSUPPORTED;
-  if (conv && (Cch % 4 || Cch <= 0 || H <= 0 || W <= 0)) return RK_EUNSUPPORTED;
-  if (splits > 1 && (flags & (SF_BIAS | SF_RELU | SF_LRELU | SF_GATE | SF_STATS | SF_BNB | SF_BNP)))
-    return RK_EBADARG;  // split-K writes raw partial slabs
-  SgParams p{};
-  p.A = A; p.B = B; p.out = C; p.bias = bias; p.stats = stats; p.gate = gate;
-  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-  p.H = H; p.W = W; p.C = Cch; p.taps = taps;
-  p.log2H = rk_log2(H); p.log2W = rk_log2(W); p.log2C = rk_log2(Cch);
-  p.invC = 1.0f / (float)Cch; p.invH = 1.0f / (float)H; p.invW = 1.0f / (float)W;
-  // reciprocal decodes are exact below 2^22 (pixel indices, tap*C column indices)
-  if (conv && (p.log2H < 0 || p.log2W < 0) && (long long)(kind == 2 ? K : M) + (long long)W * (H + 2) >= (1ll << 22))
-    return RK_EUNSUPPORTED;
-  if ((flags & SF_BNP) && (p.log2H < 0 || p.log2W < 0 || !gate || !bias || !stats)) return RK_EUNSUPPORTED;
+  if (conv && !s_map_ok(H, W, Cch)) return RK_EUNSUPPORTED;
+  if (!s_split_ok(splits, flags)) return RK_EBADARG;
+  SgParams p = s_params(A, B, C, bias, M, N, K, lda, ldb, ldc, H, W, Cch, taps, splits, slabStride, flags, alpha,
+                        slope, bytesA, bytesB);
+  p.stats = stats; p.gate = gate; p.slotMask = slotMask;
+  const bool pow2 = p.log2H >= 0 && p.log2W >= 0;  // shift decodes
+  if (conv && !pow2 && !s_decode_exact(kind == 2 ? K : M, H, W)) return RK_EUNSUPPORTED;
+  if ((flags & SF_BNP) && (!pow2 || !gate || !bias || !stats)) return RK_EUNSUPPORTED;
   if ((flags & (SF_STATS | SF_BNB)) && !stats) return RK_EBADARG;
-  p.ktPer = rk_cdiv(rk_cdiv(K, SBK), splits);
-  p.slabStride = splits > 1 ? slabStride : 0;
-  p.flags = flags; p.slotMask = slotMask; p.alpha = alpha; p.slope = slope;
-  p.bytesA = (unsigned long long)bytesA; p.bytesB = (unsigned long long)bytesB;
-  p.groups = 1;
-  p.Ho = H; p.Wo = W; p.log2Ho = p.log2H; p.log2Wo = p.log2W; p.invHo = p.invH; p.invWo = p.invW;
   hipStream_t st = (hipStream_t)stream;
   switch (kind) {
     case 0:
@@ -536,39 +560,25 @@ extern "C" int rk_sgemm_g(int kind, int tile, int nst, const float* A, const flo
                           int os, long long gstrideB, int splits, long long slabStride, int flags, float alpha,
                           float slope, long long bytesA, long long bytesB, void* stream) {
   if (kind != 6 && kind != 7) return RK_EBADARG;
-  if (bytesA <= 0 || bytesB <= 0 || bytesA >= (1ll << 31) || bytesB >= (1ll << 31)) return RK_EUNSUPPORTED;
-  if (M <= 0 || N <= 0 || K <= 0 || splits <= 0 || (nst != 2 && nst != 3) || tile < 0 ||
-      ((tile & 15) > 3 && (tile & 15) < 8) || (tile & 15) > 10 || tile > 26)
-    return RK_EBADARG;
+  if (const int e = s_check(tile, false, nst, M, N, K, splits, bytesA, bytesB)) return e;
   if (ntaps < 1 || ntaps > 16 || groups < 1 || groups > 4 || (stride != 1 && stride != 2) || (os != 1 && os != 2))
     return RK_EBADARG;
   if (kind == 7 && groups != 1) return RK_EBADARG;
-  if (Cch % 4 || Cch <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) return RK_EUNSUPPORTED;
+  if (!s_map_ok(H, W, Cch) || Ho <= 0 || Wo <= 0) return RK_EUNSUPPORTED;
   if ((kind == 6 ? K : N) != ntaps * Cch) return RK_EBADARG;
   if (kind == 6 && (lda % 4 || ldb % 4)) return RK_EUNSUPPORTED;
   if (kind == 7 && (N % 4 || M % 4 || lda % 4)) return RK_EUNSUPPORTED;
-  if (splits > 1 && (flags & (SF_BIAS | SF_RELU | SF_LRELU | SF_GATE | SF_STATS | SF_BNB | SF_BNP))) return RK_EBADARG;
+  if (!s_split_ok(splits, flags)) return RK_EBADARG;
   if (flags & (SF_GATE | SF_STATS | SF_BNB | SF_BNP)) return RK_EUNSUPPORTED;
-  // reciprocal decodes are exact below 2^22
-  const long long rows = kind == 6 ? M : K;
-  if (rows + (long long)W * (H + 2) >= (1ll << 22) || (long long)ntaps * Cch >= (1ll << 22)) return RK_EUNSUPPORTED;
-  SgParams p{};
-  p.A = A; p.B = B; p.out = C; p.bias = bias;
-  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-  p.H = H; p.W = W; p.C = Cch; p.taps = ntaps;
-  p.log2H = rk_log2(H); p.log2W = rk_log2(W); p.log2C = rk_log2(Cch);
-  p.invC = 1.0f / (float)Cch; p.invH = 1.0f / (float)H; p.invW = 1.0f / (float)W;
-  p.Ho = Ho; p.Wo = Wo; p.log2Ho = rk_log2(Ho); p.log2Wo = rk_log2(Wo);
-  p.invHo = 1.0f / (float)Ho; p.invWo = 1.0f / (float)Wo;
+  if (!s_decode_exact(kind == 6 ? M : K, H, W) || (long long)ntaps * Cch >= (1ll << 22)) return RK_EUNSUPPORTED;
+  SgParams p = s_params(A, B, C, bias, M, N, K, lda, ldb, ldc, H, W, Cch, ntaps, splits, slabStride, flags, alpha,
+                        slope, bytesA, bytesB);
+  s_row_grid(p, Ho, Wo);
   p.stride = stride; p.ntaps = ntaps; p.groups = groups; p.os = os; p.oyx = oyx; p.gstrideB = gstrideB;
   for (int g = 0; g < 4; ++g) {
     p.tpy[g] = g < groups ? tpy[g] : 0u;
     p.tpx[g] = g < groups ? tpx[g] : 0u;
   }
-  p.ktPer = rk_cdiv(rk_cdiv(K, SBK), splits);
-  p.slabStride = splits > 1 ? slabStride : 0;
-  p.flags = flags; p.alpha = alpha; p.slope = slope;
-  p.bytesA = (unsigned long long)bytesA; p.bytesB = (unsigned long long)bytesB;
   hipStream_t st = (hipStream_t)stream;
   if (kind == 6) return s_launch_tile<SM_KIN_CONVG, SM_KIN_DENSE, false>(tile, p, nst, splits, st);
   return s_launch_tile<SM_KOUT_DENSE, SM_KOUT_CONVG, false>(tile, p, nst, splits, st);
@@ -585,30 +595,17 @@ extern "C" int rk_sgemm_grp(int kind, int tile, int nst, const float* A, const f
                             long long bytesB, int groups, long long gstrideA, long long gstrideB, long long gstrideO,
                             long long gstrideBias, void* stream) {
   if (kind != 0 && kind != 3) return RK_EBADARG;
-  if (bytesA <= 0 || bytesB <= 0 || bytesA >= (1ll << 31) || bytesB >= (1ll << 31)) return RK_EUNSUPPORTED;
-  if (M <= 0 || N <= 0 || K <= 0 || splits <= 0 || (nst != 2 && nst != 3) || tile < 0 ||
-      ((tile & 15) > 3 && (tile & 15) < 8) || (tile & 15) > 10 || tile > 26)
-    return RK_EBADARG;
+  if (const int e = s_check(tile, false, nst, M, N, K, splits, bytesA, bytesB)) return e;
   if (groups < 1 || gstrideA < 0 || gstrideB < 0 || gstrideO < 0 || gstrideBias < 0) return RK_EBADARG;
   if (taps != 1 && taps != 9) return RK_EBADARG;
   if (K % 4 || lda % 4 || ldb % 4) return RK_EUNSUPPORTED;
-  if (kind == 0 && (Cch % 4 || Cch <= 0 || H <= 0 || W <= 0)) return RK_EUNSUPPORTED;
+  if (kind == 0 && !s_map_ok(H, W, Cch)) return RK_EUNSUPPORTED;
   if (flags & ~(SF_BIAS | SF_RELU | SF_LRELU)) return RK_EUNSUPPORTED;
-  if (splits > 1 && flags) return RK_EBADARG;
-  SgParams p{};
-  p.A = A; p.B = B; p.out = C; p.bias = bias;
-  p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-  p.H = H; p.W = W; p.C = Cch; p.taps = taps;
-  p.log2H = rk_log2(H); p.log2W = rk_log2(W); p.log2C = rk_log2(Cch);
-  p.invC = 1.0f / (float)Cch; p.invH = 1.0f / (float)H; p.invW = 1.0f / (float)W;
-  if (kind == 0 && (p.log2H < 0 || p.log2W < 0) && (long long)M + (long long)W * (H + 2) >= (1ll << 22))
-    return RK_EUNSUPPORTED;
-  p.ktPer = rk_cdiv(rk_cdiv(K, SBK), splits);
-  p.slabStride = splits > 1 ? slabStride : 0;
-  p.flags = flags; p.alpha = alpha; p.slope = slope;
-  p.bytesA = (unsigned long long)bytesA; p.bytesB = (unsigned long long)bytesB;
+  if (!s_split_ok(splits, flags)) return RK_EBADARG;
+  SgParams p = s_params(A, B, C, bias, M, N, K, lda, ldb, ldc, H, W, Cch, taps, splits, slabStride, flags, alpha,
+                        slope, bytesA, bytesB);
+  if (kind == 0 && (p.log2H < 0 || p.log2W < 0) && !s_decode_exact(M, H, W)) return RK_EUNSUPPORTED;
   p.groups = groups; p.gstrideA = gstrideA; p.gstrideB = gstrideB; p.gstrideO = gstrideO; p.gstrideBias = gstrideBias;
-  p.Ho = H; p.Wo = W; p.log2Ho = p.log2H; p.log2Wo = p.log2W; p.invHo = p.invH; p.invWo = p.invW;
   hipStream_t st = (hipStream_t)stream;
   if (kind == 3) return s_launch_tile<SM_KIN_DENSE, SM_KIN_DENSE, false, true>(tile, p, nst, splits, st);
   if (Cch % SBK == 0) return s_launch_tile<SM_KIN_CONVF, SM_KIN_DENSE, false, true>(tile, p, nst, splits, st);

@@ -156,6 +156,47 @@ def _slots_flags(acc):
     return 0 if acc is None else acc.shape[0] - 1
 
 
+def _act_flags(bias, act):
+    return (F_BIAS if bias is not None else 0) | (F_RELU if act == ACT_RELU else F_LRELU if act == ACT_LRELU else 0)
+
+
+def _sum_slabs(launch, out, splits, accumulate):
+    """A weight gradient over ``splits`` K ranges: ``launch(dst, accumulate)`` computes out (+)= the product when
+    splits == 1, else one raw slab of out's shape per split, which reduce_slabs sums into out."""
+    if splits == 1:
+        launch(out, bool(accumulate))
+        return out
+    slab = torch.empty((splits,) + tuple(out.shape), device=out.device, dtype=torch.float32)
+    launch(slab, False)
+    return reduce_slabs(slab, out, accumulate=accumulate)
+
+
+def _gemm(cfg, launch, out, M, N, *, groups=1, ldc=None, accumulate=None, stats=None, bias=None, act=ACT_NONE,
+          slope=0.2, alpha=1.0, gate=None, bias_rows=0):
+    """One direct fp32 GEMM under cfg = (tile code, ring depth, K splits).  ``launch(dst, ldc, **kw)`` is the op's
+    statement of it, an sgemm / sgemm_g / sgemm_grp call less where it writes and how: ``groups`` stacked [M][N]
+    products into out, [groups * M][N] of row stride ``ldc`` (default N).  Its epilogue is ``accumulate`` (a weight
+    gradient: out (+)= the product) or what sreduce_epi applies (bias, act, slope, alpha, gate, bias_rows), with
+    ``stats`` (BN statistics, never split).  Unsplit, the epilogue rides in the kernel; split, the kernel writes raw
+    slabs [splits][groups * M][N] and the combine (reduce_slabs / sreduce_epi) applies it."""
+    tile, nst, s = cfg
+    rows = groups * M
+    split = dict(splits=s, slab_stride=rows * N) if s > 1 else {}
+    if accumulate is not None:
+        _sum_slabs(lambda dst, acc: launch(dst, N, tile=tile, nst=nst, flags=F_ACCUM if acc else 0, **split),
+                   out, s, accumulate)
+    elif s == 1:
+        own = {k: v for k, v in (('gate', gate), ('stats', stats)) if v is not None}   # rk_sgemm's alone
+        flags = _act_flags(bias, act) | (F_GATE if gate is not None else 0) | (F_STATS if stats is not None else 0)
+        launch(out, ldc or N, tile=tile, nst=nst, bias=bias, flags=flags, slope=slope, alpha=alpha, **own)
+    else:
+        assert stats is None
+        slab = torch.empty((s, rows, N), device=out.device, dtype=torch.float32)
+        launch(slab, N, tile=tile, nst=nst, **split)
+        sreduce_epi(slab, rows, N, out if out.dim() == 2 else out.view(rows, N), bias=bias, act=act, slope=slope,
+                    alpha=alpha, gate=gate, bias_rows=bias_rows)
+
+
 # ------------------------------------------------------------------------------------------ conv
 # cfg[0] >= 0 is the direct implicit-GEMM kernel, cfg = (tile code, ring depth, K splits); cfg[0] < 0 names a
 # route of CONV_ROUTES / WGRAD_ROUTES (the route table below), which also says what cfg[1:] hold.
@@ -265,8 +306,7 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, *, taps: int = 9, stats_acc=None,
     assert w.numel() == Cout * K, (w.shape, taps, Cin)
     if out is None:
         out = torch.empty((Nb, H, W, Cout), device=x.device, dtype=torch.float32)
-    flags = (F_STATS if stats_acc is not None else 0) | (F_BIAS if bias is not None else 0)
-    flags |= F_RELU if act == ACT_RELU else F_LRELU if act == ACT_LRELU else 0
+    flags = _act_flags(bias, act) | (F_STATS if stats_acc is not None else 0)
     sets = (wino, wino4, wino4p, wino4b)
     epi = dict(bias=bias, stats=stats_acc, relu=act == ACT_RELU)
     need = 0
@@ -287,17 +327,10 @@ def conv_fwd(x: torch.Tensor, w: torch.Tensor, *, taps: int = 9, stats_acc=None,
         if r is not None:
             _run_route(r, x, sets, out, cfg, epi)
             return
-        tile, nst, s = cfg
-        if s == 1:
-            sgemm(KIND_CONV, x, w, out, M, Cout, K, Cin, K, Cout, tile=tile, nst=nst, bias=bias, stats=stats_acc,
-                  H=H, W=W, C=Cin, taps=taps, flags=flags, slope=slope)
-            return
-        # small-M deep layers (inference at small batch: 4x4 maps, K = 9 x 512): split-K slabs + one
-        # combine that applies bias / activation
-        slab = torch.empty((s, M, Cout), device=x.device, dtype=torch.float32)
-        sgemm(KIND_CONV, x, w, slab, M, Cout, K, Cin, K, Cout, tile=tile, nst=nst, splits=s, slab_stride=M * Cout,
-              H=H, W=W, C=Cin, taps=taps)
-        sreduce_epi(slab, M, Cout, out.view(M, Cout), bias=bias, act=act, slope=slope)
+        # split-K: small-M deep layers (inference at small batch: 4x4 maps, K = 9 x 512)
+        _gemm(cfg, lambda dst, ldc, **kw: sgemm(KIND_CONV, x, w, dst, M, Cout, K, Cin, K, ldc, H=H, W=W, C=Cin,
+                                                taps=taps, **kw),
+              out, M, Cout, stats=stats_acc, bias=bias, act=act, slope=slope)
     cfg = _pick(('sf', M, Cout, K, H, W, Cin, taps, flags) + _sets_key(sets, on)
                 + (('pro',) if pro is not None else ()), cands, run)
     if stats_acc is not None and autotune.can_tune():
@@ -322,18 +355,10 @@ def conv_dgrad(dy: torch.Tensor, wt, *, taps: int = 9, out=None, gate=None, bnb=
     assert callable(wt) or wt.numel() == Cin * K
     if out is None:
         out = torch.empty((Nb, H, W, Cin), device=dy.device, dtype=torch.float32)
-    flags, bias, stats = 0, None, None
-    if bnb is not None:
-        y, coeffs, stats = bnb
-        assert y.shape == out.shape and stats.dtype == torch.float64 and stats.shape[-1] == Cin
-        gate, bias, flags = y, coeffs[2:4].reshape(-1), F_BNB
-    elif bnp is not None:
-        y, coeffs, stats = bnp
-        assert y.shape == (Nb, 2 * H, 2 * W, Cin) and stats.dtype == torch.float64
-        assert not (H & (H - 1)) and not (W & (W - 1)), 'pooled BN fusion needs power-of-two maps'
-        gate, bias, flags = y, coeffs[2:4].reshape(-1), F_BNP
-    elif gate is not None:
-        flags = F_GATE
+    flags, bias, stats = F_GATE if gate is not None else 0, None, None
+    if bnb is not None or bnp is not None:
+        assert bnb is not None or (not (H & (H - 1)) and not (W & (W - 1))), 'pooled BN fusion needs power-of-two maps'
+        flags, bias, stats, gate = _bn_bwd_epilogue(out, bnb, bnp)
     sets = (wino, wino4, wino4p, wino4b)
     epi = dict(bnb=bnb, bnp=bnp)
     on, fused = _offered(CONV_FAMILIES, sets, taps, H, W, Cout, Cin, E_DIRECT if flags & F_GATE else 0)
@@ -391,15 +416,9 @@ def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, *, taps: int = 9, out=None, ac
         if r is not None:
             r.kernel(dy, x, out, accumulate=accumulate, **SLOTS[r.slots](r, cfg), **pro)
             return
-        tile, nst, s = cfg
-        if s == 1:
-            sgemm(KIND_WGRAD, dy, x, out, M, N, K, Cout, Cin, N, tile=tile, nst=nst, H=H, W=W, C=Cin, taps=taps,
-                  flags=F_ACCUM if accumulate else 0)
-            return
-        slab = torch.empty((s, M, N), device=dy.device, dtype=torch.float32)
-        sgemm(KIND_WGRAD, dy, x, slab, M, N, K, Cout, Cin, N, tile=tile, nst=nst, splits=s, slab_stride=M * N,
-              H=H, W=W, C=Cin, taps=taps)
-        reduce_slabs(slab, out, accumulate=accumulate)
+        _gemm(cfg, lambda dst, ldc, **kw: sgemm(KIND_WGRAD, dy, x, dst, M, N, K, Cout, Cin, ldc, H=H, W=W, C=Cin,
+                                                taps=taps, **kw),
+              out, M, N, accumulate=bool(accumulate))
     cfg = _pick(('sw', M, N, K, H, W, Cin, taps, bool(accumulate)) + tuple(bool(f) for f in found)
                 + (('pro',) if pro else ()), cands, run, protect=(out,) if accumulate else ())
     run(cfg)
@@ -484,20 +503,24 @@ def wino_ut(w: torch.Tensor) -> torch.Tensor:
     return wino_set('ut2', w)
 
 
+def _bn_bwd_epilogue(out, bnb, bnp):
+    """(flags, bias, stats, gate) of a data gradient into a BN+ReLU layer, ``bnb`` = (y, coeffs, acc), or into
+    maxpool(BN+ReLU(y)) with y at 2x resolution, ``bnp``: gate = y, bias = BN scale | shift, the sums go to acc.
+    The flag is F_BNB / F_BNP, the same bits as WF_BNB / WF_BNP."""
+    y, coeffs, stats = bnb if bnb is not None else bnp
+    Nb, H, W, N = out.shape
+    assert y.shape == (out.shape if bnb is not None else (Nb, 2 * H, 2 * W, N))
+    assert stats.dtype == torch.float64 and stats.shape[-1] == N
+    return F_BNB if bnb is not None else F_BNP, coeffs[2:4].reshape(-1).contiguous(), stats, y
+
+
 def _wino_epilogue(out, bias, stats, relu, bnb, bnp):
     """(flags, bias, stats, gate) of a Winograd conv's epilogue: bias / ReLU / BN statistics, or with ``bnb``
     / ``bnp`` = (y, coeffs, acc) the BN-backward forms of conv_dgrad (gate = y, bias = BN scale | shift)."""
     flags = (WF_BIAS if bias is not None else 0) | (WF_RELU if relu else 0) | (WF_STATS if stats is not None else 0)
     gate = None
-    if bnb is not None:
-        gate, coeffs, stats = bnb
-        assert gate.shape == out.shape
-        bias, flags = coeffs[2:4].reshape(-1).contiguous(), WF_BNB
-    elif bnp is not None:
-        gate, coeffs, stats = bnp
-        Nb, H, W, N = out.shape
-        assert gate.shape == (Nb, 2 * H, 2 * W, N)
-        bias, flags = coeffs[2:4].reshape(-1).contiguous(), WF_BNP
+    if bnb is not None or bnp is not None:
+        flags, bias, stats, gate = _bn_bwd_epilogue(out, bnb, bnp)
     if stats is not None:
         assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.shape[-1] == out.shape[-1]
     return flags, bias, stats, gate
@@ -725,15 +748,9 @@ def wino4_wgrad(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor, *, splits=
     Cin = x.shape[-1]
     assert x.shape[:3] == dy.shape[:3] and out.numel() == Cout * 9 * Cin and out.is_contiguous()
     assert xpro is None or (xpro.shape == (4, Cin) and xpro.is_contiguous() and variant in (0, 1))
-    if splits == 1:
-        dst, acc = out, int(bool(accumulate))
-    else:
-        dst, acc = torch.empty((splits, Cout, 9 * Cin), device=dy.device, dtype=torch.float32), 0
-    _lib.call("rk_wino4_wgrad", _p(dy), _p(x), _p(dst), Nb, H, W, Cout, Cin, int(splits), acc, int(variant),
-              _pro(xpro), _s())
-    if splits != 1:
-        reduce_slabs(dst, out.view(Cout, 9 * Cin), accumulate=accumulate)
-    return out
+    return _sum_slabs(lambda dst, acc: _lib.call("rk_wino4_wgrad", _p(dy), _p(x), _p(dst), Nb, H, W, Cout, Cin,
+                                                 int(splits), int(acc), int(variant), _pro(xpro), _s()),
+                      out, splits, accumulate)
 
 
 def _wino4_pt_cands(Nb, H, W, Cout, Cin):
@@ -905,13 +922,9 @@ def wino_wgrad(dy: torch.Tensor, x: torch.Tensor, out: torch.Tensor, *, splits=1
     Nb, H, W, Cout = dy.shape
     Cin = x.shape[-1]
     assert x.shape[:3] == dy.shape[:3] and out.numel() == Cout * 9 * Cin and out.is_contiguous()
-    if splits == 1:
-        _lib.call("rk_wino_wgrad", _p(dy), _p(x), _p(out), Nb, H, W, Cout, Cin, 1, int(bool(accumulate)), _s())
-        return out
-    slab = torch.empty((splits, Cout, 9 * Cin), device=dy.device, dtype=torch.float32)
-    _lib.call("rk_wino_wgrad", _p(dy), _p(x), _p(slab), Nb, H, W, Cout, Cin, int(splits), 0, _s())
-    reduce_slabs(slab, out.view(Cout, 9 * Cin), accumulate=accumulate)
-    return out
+    return _sum_slabs(lambda dst, acc: _lib.call("rk_wino_wgrad", _p(dy), _p(x), _p(dst), Nb, H, W, Cout, Cin,
+                                                 int(splits), int(acc), _s()),
+                      out, splits, accumulate)
 
 
 def wino_conv_grp(x, u, *, out=None, bias=None, relu=False, variant=0, pool=False):
@@ -1155,6 +1168,14 @@ def _xpd(cfg):
     return cfg[0] == XP_DENSE
 
 
+def _offer_xpd(key, cands, macs, fits=True):
+    """(key, candidates) of a dense op, with the pre-split X6 candidates where the GEMM is big enough to pay for
+    the split passes and ``fits`` them (the op's own conditions): the key then says so."""
+    if fits and macs >= XPD_MIN_MACS:
+        return key + ('xp',), cands + list(XPD_CFGS)
+    return key, cands
+
+
 def _xp_gemm_into(A, B, M, N, K, code, s, out=None, accumulate=False):
     """x6p GEMM of planes A [3][M][K] . B [3][N][K]^T: into ``out`` (s == 1) or a fresh [s][M][N] slab."""
     s = x6p_splits(K, s)
@@ -1173,27 +1194,19 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias=None, *, act=ACT_NONE, slope=0
     N = w.shape[0]
     if out is None:
         out = torch.empty((M, N), device=x.device, dtype=torch.float32)
-    flags = (F_BIAS if bias is not None else 0) | (F_RELU if act == ACT_RELU else F_LRELU if act == ACT_LRELU else 0)
+    epi = dict(bias=bias, act=act, slope=slope, alpha=alpha)
 
     def run(cfg):
-        tile, nst, s = cfg
         if _xpd(cfg):
-            slab, _ = _xp_gemm_into(x6p_split(x), x6p_split(w), M, N, K, nst, s)
-            sreduce_epi(slab, M, N, out, bias=bias, act=act, slope=slope, alpha=alpha)
+            slab, _ = _xp_gemm_into(x6p_split(x), x6p_split(w), M, N, K, cfg[1], cfg[2])
+            sreduce_epi(slab, M, N, out, **epi)
             return
-        if s == 1:
-            sgemm(KIND_DENSE, x, w, out, M, N, K, x.stride(0), w.stride(0), out.stride(0), tile=tile, nst=nst,
-                  bias=bias, flags=flags, slope=slope, alpha=alpha)
-            return
-        slab = torch.empty((s, M, N), device=x.device, dtype=torch.float32)
-        sgemm(KIND_DENSE, x, w, slab, M, N, K, x.stride(0), w.stride(0), N, tile=tile, nst=nst, splits=s,
-              slab_stride=M * N)
-        sreduce_epi(slab, M, N, out, bias=bias, act=act, slope=slope, alpha=alpha)
-    cands = _cands(M, N, splittable=N % 4 == 0 and out.stride(0) % 4 == 0, K=K)
-    xp = K % 32 == 0 and x.is_contiguous() and w.is_contiguous() and M * N * K >= XPD_MIN_MACS
-    if xp:
-        cands = cands + list(XPD_CFGS)
-    run(_pick(('sl', M, N, K, act, bias is not None, float(alpha)) + (('xp',) if xp else ()), cands, run))
+        _gemm(cfg, lambda dst, ldc, **kw: sgemm(KIND_DENSE, x, w, dst, M, N, K, x.stride(0), w.stride(0), ldc, **kw),
+              out, M, N, ldc=out.stride(0), **epi)
+    key, cands = _offer_xpd(('sl', M, N, K, act, bias is not None, float(alpha)),
+                            _cands(M, N, splittable=N % 4 == 0 and out.stride(0) % 4 == 0, K=K), M * N * K,
+                            K % 32 == 0 and x.is_contiguous() and w.is_contiguous())
+    run(_pick(key, cands, run))
     return out
 
 
@@ -1205,24 +1218,16 @@ def linear_dx(dy: torch.Tensor, w: torch.Tensor, *, gate=None, out=None):
         out = torch.empty((M, Nin), device=dy.device, dtype=torch.float32)
 
     def run(cfg):
-        tile, nst, s = cfg
         if _xpd(cfg):
-            slab, _ = _xp_gemm_into(x6p_split(dy), x6p_split_t(w), M, Nin, Nout, nst, s)
+            slab, _ = _xp_gemm_into(x6p_split(dy), x6p_split_t(w), M, Nin, Nout, cfg[1], cfg[2])
             sreduce_epi(slab, M, Nin, out, gate=gate)
             return
-        if s == 1:
-            sgemm(KIND_DENSE_DX, dy, w, out, M, Nin, Nout, dy.stride(0), w.stride(0), out.stride(0), tile=tile,
-                  nst=nst, gate=gate, flags=F_GATE if gate is not None else 0)
-            return
-        slab = torch.empty((s, M, Nin), device=dy.device, dtype=torch.float32)
-        sgemm(KIND_DENSE_DX, dy, w, slab, M, Nin, Nout, dy.stride(0), w.stride(0), Nin, tile=tile, nst=nst,
-              splits=s, slab_stride=M * Nin)
-        sreduce_epi(slab, M, Nin, out, gate=gate)
-    cands = _cands(M, Nin, splittable=Nin % 4 == 0, K=Nout)
-    xp = Nout % 32 == 0 and dy.is_contiguous() and w.is_contiguous() and M * Nin * Nout >= XPD_MIN_MACS
-    if xp:
-        cands = cands + list(XPD_CFGS)
-    run(_pick(('sx', M, Nin, Nout, gate is not None) + (('xp',) if xp else ()), cands, run))
+        _gemm(cfg, lambda dst, ldc, **kw: sgemm(KIND_DENSE_DX, dy, w, dst, M, Nin, Nout, dy.stride(0), w.stride(0),
+                                                ldc, **kw),
+              out, M, Nin, ldc=out.stride(0), gate=gate)
+    key, cands = _offer_xpd(('sx', M, Nin, Nout, gate is not None), _cands(M, Nin, splittable=Nin % 4 == 0, K=Nout),
+                            M * Nin * Nout, Nout % 32 == 0 and dy.is_contiguous() and w.is_contiguous())
+    run(_pick(key, cands, run))
     return out
 
 
@@ -1234,28 +1239,19 @@ def linear_dw(dy: torch.Tensor, x: torch.Tensor, *, out=None, accumulate=False):
         out = torch.empty((Nout, Nin), device=dy.device, dtype=torch.float32)
 
     def run(cfg):
-        tile, nst, s = cfg
         if _xpd(cfg):
             Mp = cdiv(M, 32) * 32
-            res, k = _xp_gemm_into(x6p_split_t(dy, Mp), x6p_split_t(x, Mp), Nout, Nin, Mp, nst, s,
+            res, k = _xp_gemm_into(x6p_split_t(dy, Mp), x6p_split_t(x, Mp), Nout, Nin, Mp, cfg[1], cfg[2],
                                    out=out if out.is_contiguous() else None, accumulate=accumulate)
             if k > 1 or res is not out:
                 reduce_slabs(res, out, accumulate=accumulate)
             return
-        if s == 1:
-            sgemm(KIND_DENSE_DW, dy, x, out, Nout, Nin, M, dy.stride(0), x.stride(0), Nin, tile=tile, nst=nst,
-                  flags=F_ACCUM if accumulate else 0)
-            return
-        slab = torch.empty((s, Nout, Nin), device=dy.device, dtype=torch.float32)
-        sgemm(KIND_DENSE_DW, dy, x, slab, Nout, Nin, M, dy.stride(0), x.stride(0), Nin, tile=tile, nst=nst,
-              splits=s, slab_stride=Nout * Nin)
-        reduce_slabs(slab, out, accumulate=accumulate)
-    cands = _cands(Nout, Nin, splittable=True, K=M)
-    xp = Nout * Nin * M >= XPD_MIN_MACS
-    if xp:
-        cands = cands + list(XPD_CFGS)
-    run(_pick(('sdw', M, Nout, Nin, bool(accumulate)) + (('xp',) if xp else ()), cands, run,
-              protect=(out,) if accumulate else ()))
+        _gemm(cfg, lambda dst, ldc, **kw: sgemm(KIND_DENSE_DW, dy, x, dst, Nout, Nin, M, dy.stride(0), x.stride(0),
+                                                ldc, **kw),
+              out, Nout, Nin, accumulate=bool(accumulate))
+    key, cands = _offer_xpd(('sdw', M, Nout, Nin, bool(accumulate)), _cands(Nout, Nin, splittable=True, K=M),
+                            Nout * Nin * M)
+    run(_pick(key, cands, run, protect=(out,) if accumulate else ()))
     return out
 
 
@@ -1539,10 +1535,6 @@ def sgemm_g(kind, A, B, out, M, N, K, lda, ldb, ldc, H, W, C, Ho, Wo, stride, nt
     return out
 
 
-def _act_flags(bias, act):
-    return (F_BIAS if bias is not None else 0) | (F_RELU if act == ACT_RELU else F_LRELU if act == ACT_LRELU else 0)
-
-
 def s2_conv(x, W, *, bias=None, act=ACT_NONE, slope=0.2, out=None):
     """S2: x [N, H, W, Ci] -> [N, H/2, W/2, Co] with W [Co, 16*Ci] (+bias, act)."""
     _check(x, 's2_conv x')
@@ -1556,14 +1548,9 @@ def s2_conv(x, W, *, bias=None, act=ACT_NONE, slope=0.2, out=None):
     flags = _act_flags(bias, act)
 
     def run(cfg):
-        tile, nst, s = cfg
-        geo = (H, Wd, Ci, Ho, Wo, 2, 16, [_S2_TPY], [_S2_TPX])
-        if s == 1:
-            sgemm_g(6, x, W, out, M, Co, K, Ci, K, Co, *geo, tile=tile, nst=nst, bias=bias, flags=flags, slope=slope)
-            return
-        slab = torch.empty((s, M, Co), device=x.device, dtype=torch.float32)
-        sgemm_g(6, x, W, slab, M, Co, K, Ci, K, Co, *geo, tile=tile, nst=nst, splits=s, slab_stride=M * Co)
-        sreduce_epi(slab, M, Co, out.view(M, Co), bias=bias, act=act, slope=slope)
+        _gemm(cfg, lambda dst, ldc, **kw: sgemm_g(6, x, W, dst, M, Co, K, Ci, K, ldc, H, Wd, Ci, Ho, Wo, 2, 16,
+                                                  [_S2_TPY], [_S2_TPX], **kw),
+              out, M, Co, bias=bias, act=act, slope=slope)
     run(_pick(('s2f', M, Co, K, H, Wd, Ci, flags), _cands(M, Co, splittable=Co % 4 == 0, K=K), run))
     return out
 
@@ -1588,18 +1575,11 @@ def s2t_conv(z, W, *, bias=None, act=ACT_NONE, slope=0.2, out=None, wr=None):
     if out is None:
         out = torch.empty((Nb, 2 * h, 2 * w, Ci), device=z.device, dtype=torch.float32)
     flags = _act_flags(bias, act)
-    geo = (h, w, Co, h, w, 1, 4, _S2T_TPY, _S2T_TPX)
-    kw = dict(groups=4, oyx=_S2T_OYX, os_=2, gstride_b=Ci * K)
 
     def run(cfg):
-        tile, nst, s = cfg
-        if s == 1:
-            sgemm_g(6, z, wr, out, M, Ci, K, Co, K, Ci, *geo, tile=tile, nst=nst, bias=bias, flags=flags, slope=slope,
-                    **kw)
-            return
-        slab = torch.empty((s, 4 * M, Ci), device=z.device, dtype=torch.float32)
-        sgemm_g(6, z, wr, slab, M, Ci, K, Co, K, Ci, *geo, tile=tile, nst=nst, splits=s, slab_stride=4 * M * Ci, **kw)
-        sreduce_epi(slab, 4 * M, Ci, out.view(4 * M, Ci), bias=bias, act=act, slope=slope)
+        _gemm(cfg, lambda dst, ldc, **kw: sgemm_g(6, z, wr, dst, M, Ci, K, Co, K, ldc, h, w, Co, h, w, 1, 4, _S2T_TPY,
+                                                  _S2T_TPX, groups=4, oyx=_S2T_OYX, os_=2, gstride_b=Ci * K, **kw),
+              out, M, Ci, groups=4, bias=bias, act=act, slope=slope)
     run(_pick(('s2t', M, Ci, K, h, w, Co, flags), _cands(M, Ci, splittable=Ci % 4 == 0, K=K), run))
     return out
 
@@ -1615,16 +1595,11 @@ def s2_wgrad(x, g, *, out=None):
     M, N, K = Co, 16 * Ci, Nb * Ho * Wo
     if out is None:
         out = torch.empty((Co, N), device=x.device, dtype=torch.float32)
-    geo = (H, Wd, Ci, Ho, Wo, 2, 16, [_S2_TPY], [_S2_TPX])
 
     def run(cfg):
-        tile, nst, s = cfg
-        if s == 1:
-            sgemm_g(7, g, x, out, M, N, K, Co, Ci, N, *geo, tile=tile, nst=nst)
-            return
-        slab = torch.empty((s, M, N), device=x.device, dtype=torch.float32)
-        sgemm_g(7, g, x, slab, M, N, K, Co, Ci, N, *geo, tile=tile, nst=nst, splits=s, slab_stride=M * N)
-        reduce_slabs(slab, out)
+        _gemm(cfg, lambda dst, ldc, **kw: sgemm_g(7, g, x, dst, M, N, K, Co, Ci, ldc, H, Wd, Ci, Ho, Wo, 2, 16,
+                                                  [_S2_TPY], [_S2_TPX], **kw),
+              out, M, N, accumulate=False)
     run(_pick(('s2w', M, N, K, H, Wd, Ci), _lead_with_split(_cands(M, N, splittable=True, K=K), M, N), run))
     return out
 
@@ -1678,22 +1653,18 @@ def _grp_run(kind, A, B, out, M, N, K, lda, ldb, G, gsa, key, *, bias=None, act=
              fused=None):
     """Autotuned grouped launch: out [G, M, N]; split-K slabs [s, G*M, N] combined by sreduce_epi with
     per-group bias.  ``fused`` = (candidates, weight sets, epilogue): the grouped rows of CONV_ROUTES."""
-    flags = _act_flags(bias, act)
     geo = geo or {}
+
+    def gemm(dst, ldc, splits=1, **kw):
+        # gstride_bias: a split launch takes no bias (its combine finds group g's by ``bias_rows``)
+        return sgemm_grp(kind, A, B, dst, M, N, K, lda, ldb, ldc, G, gsa, N * K, M * N, N if splits == 1 else 0,
+                         splits=splits, **geo, **kw)
 
     def run(cfg):
         if cfg[0] in CONV_ROUTES:
             _run_grp_route(cfg, A, fused[1], out, fused[2])
             return
-        tile, nst, s = cfg
-        if s == 1:
-            sgemm_grp(kind, A, B, out, M, N, K, lda, ldb, N, G, gsa, N * K, M * N, N, tile=tile, nst=nst,
-                      bias=bias, flags=flags, slope=slope, **geo)
-            return
-        slab = torch.empty((s, G * M, N), device=out.device, dtype=torch.float32)
-        sgemm_grp(kind, A, B, slab, M, N, K, lda, ldb, N, G, gsa, N * K, M * N, 0, tile=tile, nst=nst, splits=s,
-                  slab_stride=G * M * N, **geo)
-        sreduce_epi(slab, G * M, N, out.view(G * M, N), bias=bias, act=act, slope=slope, bias_rows=M)
+        _gemm(cfg, gemm, out, M, N, groups=G, bias=bias, act=act, slope=slope, bias_rows=M)
     cands = [c for c in _cands(M * G, N, splittable=N % 4 == 0, K=K) if (c[0] & 15) < 4 or (c[0] & 15) in _FEW_WAVE]
     if fused is not None:
         cands.extend(fused[0])
