@@ -7,6 +7,9 @@
 //  * rk_sgd_step / rk_adam_step: multi-tensor optimizer over ONE flat parameter buffer — fp32
 //    master weights, fp32 grads and state, plus the bf16 compute copy written in the same pass
 //    (so the next forward never needs a separate cast kernel).  16-byte vectors, grid-stride.
+//  * rk_grad_sumsq + rk_sgd_step_clip / rk_adam_step_clip: global-norm gradient clipping on the device — a
+//    deterministic fp64 sum of squares of the gradient arena into <= 256 partials, folded by every block of the
+//    optimizer launch into the clip coefficient (no host sync, graph-capturable, no atomics).
 //  * rk_lerp (Gs EMA, pg_gans.py:730-740), rk_nonfinite_count (pg_gans.py:1180-1191),
 //    rk_reduce_slabs (split-K combine), rk_colsum (bias grads), rk_ensemble_mean (predictor).
 #include "common.h"
@@ -113,14 +116,107 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
   }
 }
 
+// ---- global-norm gradient clipping ----------------------------------------------------------------------
+// Stage 1 (grad_sumsq_kernel): part[b] = sum of g^2 over block b's share of the n fp32 values, squares formed and
+// summed in fp64 ((double)g * g: finite for any finite fp32 g, and n * 2^-53 of rounding is far below fp32's
+// 2^-24).  The order is fixed — thread t of block b sums vectors b * 256 + t, + grid, ... into one chain per vector
+// lane and per unrolled trip, then the wave's butterfly, then the four wave sums in order — and the grid is a
+// function of n alone (sumsq_parts), so the same gradients give the same bits on every replay and every device.
+// Stage 2 (grad_clip_coef, inside the optimizer launch): every block folds the <= 256 partials in one fixed
+// shape (thread t takes part[t], butterfly, four wave sums), so all blocks agree on
+//   norm = (float)sqrt(total),  coef = min(1, max_norm / (norm + 1e-6))      (torch's clip_grad_norm_)
+// without a grid-wide fence; max_norm = +inf gives coef = 1 exactly (measure only).
+RK_DEV double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+int sumsq_parts(long long n) {
+  const long long p = (n / 4 + 255) / 256;
+  return (int)(p < 1 ? 1 : p > 256 ? 256 : p);
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, long long n,
+                                                         double* __restrict__ part) {
+  __shared__ double red[4];
+  const long long n4 = n >> 2, stride = (long long)gridDim.x * 256;
+  double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  for (; i + stride < n4; i += 2 * stride) {  // two independent loads and chains in flight
+    const f32x4 p = ((const f32x4*)g)[i], q = ((const f32x4*)g)[i + stride];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      a[e] += (double)p[e] * (double)p[e];
+      b[e] += (double)q[e] * (double)q[e];
+    }
+  }
+  if (i < n4) {
+    const f32x4 p = ((const f32x4*)g)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a[e] += (double)p[e] * (double)p[e];
+  }
+  const double s = wave_sum_f64(((a[0] + a[1]) + (a[2] + a[3])) + ((b[0] + b[1]) + (b[2] + b[3])));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// CLIP = true (rk_sgd_step_clip, rk_adam_step_clip): the optimizer kernels below with gscale * coef in place of
+// gscale; the per-element arithmetic is the same text, so a clipped step gives the bits of the unclipped entry
+// point called with grad_scale = coef.
+//   stats (nullable; block 0, thread 0, plain stores) [8] floats: last norm, last coef, sum and max of the finite
+//   norms, steps with coef < 1, skipped steps, steps, unused.
+template <bool CLIP> struct GradClip {};
+template <> struct GradClip<true> {
+  const double* part;  // [nparts] of grad_sumsq_kernel over the WHOLE gradient arena
+  int nparts;          // <= 256 = the block size of the optimizer kernels
+  float max_norm;
+  float* stats;
+};
+
+// false: the norm is not finite (an inf or NaN gradient, or a norm beyond fp32) and the step is skipped.
+// Every thread of the block must call it (one barrier).
+RK_DEV bool grad_clip_coef(const GradClip<true>& c, float& coef) {
+  __shared__ double red[4];
+  const double s = wave_sum_f64((int)threadIdx.x < c.nparts ? c.part[threadIdx.x] : 0.0);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+  const bool ok = isfinite(norm);
+  coef = ok ? fminf(1.f, c.max_norm / (norm + 1e-6f)) : 0.f;
+  if (c.stats && blockIdx.x == 0 && threadIdx.x == 0) {
+    float* st = c.stats;
+    st[0] = norm;
+    st[1] = coef;
+    if (ok) {
+      st[2] += norm;
+      st[3] = fmaxf(st[3], norm);
+      if (coef < 1.f) st[4] += 1.f;
+    } else {
+      st[5] += 1.f;
+    }
+    st[6] += 1.f;
+  }
+  return ok;
+}
+
 // One launch over the whole arena: weight decay applies to elements [0, decay_end) (the arena puts
 // decayed parameters first).  bump: a device step counter advanced once (the last kernel of a
-// scheduled training step owns it, so no separate increment launch is needed).
+// scheduled training step owns it, so no separate increment launch is needed) — also when a clipped step is
+// skipped.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ w, bf16* __restrict__ wb,
                                                   const float* __restrict__ g, float* __restrict__ mom, long long n,
                                                   float lr, float momentum, float wd, int nesterov, float gscale,
-                                                  const float* lr_ptr, long long decay_end, int* bump) {
+                                                  const float* lr_ptr, long long decay_end, int* bump,
+                                                  const GradClip<CLIP> clip) {
   if (bump && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(bump, 1);
+  if constexpr (CLIP) {
+    float coef;
+    if (!grad_clip_coef(clip, coef)) return;
+    gscale *= coef;
+  }
   const float lrv = lr_ptr ? lr_ptr[0] * lr : lr;
   const long long n4 = n >> 2;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
@@ -144,13 +240,19 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ w, bf16* _
 
 // omb1 / omb2: 1 - beta as computed on the host in double (torch's Adam adds (1 - beta) * g the same
 // way); forming 1 - b2 from the fp32 b2 here would cancel to 1.3e-5 relative error at b2 = 0.999
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, bf16* __restrict__ wb,
                                                    const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, long long n, float lr, float b1, float b2,
                                                    float omb1, float omb2, float eps, float wd, int decoupled,
                                                    float c1, float c2, float gscale, const int* skip,
-                                                   const int* step_ptr) {
+                                                   const int* step_ptr, const GradClip<CLIP> clip) {
   if (skip && skip[0] != 0) return;  // non-finite gradients: skip the update (pg_gans.py:1180-1191)
+  if constexpr (CLIP) {  // a non-finite norm skips the same way: the caller's step counter stays advanced
+    float coef;
+    if (!grad_clip_coef(clip, coef)) return;
+    gscale *= coef;
+  }
   if (step_ptr) {  // device-side step counter: bias corrections survive hipGraph replay (in double:
                    // 1 - beta^t cancels at small t)
     const int t = step_ptr[0];
@@ -798,22 +900,76 @@ extern "C" int rk_softmax_xent_f32s(const float* logits, int ldl, const int* lab
   return RK_OK;
 }
 
+template <bool CLIP>
+static int sgd_launch(float* w, void* wb, const float* g, float* mom, long long n, float lr, float momentum, float wd,
+                      int nesterov, float gscale, const float* lr_ptr, long long decay_end, int* bump,
+                      const GradClip<CLIP> clip, void* stream) {
+  if (n % 4 || decay_end % 4) return RK_EUNSUPPORTED;
+  hipLaunchKernelGGL(sgd_kernel<CLIP>, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream, w, (bf16*)wb,
+                     g, mom, n, lr, momentum, wd, nesterov, gscale, lr_ptr, decay_end, bump, clip);
+  RK_LAUNCH_CHECK();
+  return RK_OK;
+}
+
+template <bool CLIP>
+static int adam_launch(float* w, void* wb, const float* g, float* m, float* v, long long n, float lr, float b1,
+                       float b2, float omb1, float omb2, float eps, float wd, int decoupled, float c1, float c2,
+                       float gscale, const int* skip, const int* step_ptr, const GradClip<CLIP> clip, void* stream) {
+  if (n % 4) return RK_EUNSUPPORTED;
+  hipLaunchKernelGGL(adam_kernel<CLIP>, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream, w, (bf16*)wb,
+                     g, m, v, n, lr, b1, b2, omb1, omb2, eps, wd, decoupled, c1, c2, gscale, skip, step_ptr, clip);
+  RK_LAUNCH_CHECK();
+  return RK_OK;
+}
+
+// partials of rk_grad_sumsq (over the whole gradient arena, which may be longer than this launch's range), a
+// max_norm > 0 (+inf: measure only) and the nullable stats block
+static bool clip_args(const double* partials, int nparts, float max_norm, float* stats, GradClip<true>& c) {
+  if (!partials || nparts < 1 || nparts > 256 || !(max_norm > 0.f)) return false;
+  c.part = partials, c.nparts = nparts, c.max_norm = max_norm, c.stats = stats;
+  return true;
+}
+
 extern "C" int rk_sgd_step(float* w, void* wb, const float* g, float* mom, long long n, float lr, float momentum,
                            float wd, int nesterov, float gscale, const float* lr_ptr, long long decay_end, int* bump,
                            void* stream) {
-  if (n % 4 || decay_end % 4) return RK_EUNSUPPORTED;
-  hipLaunchKernelGGL(sgd_kernel, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream, w, (bf16*)wb, g, mom,
-                     n, lr, momentum, wd, nesterov, gscale, lr_ptr, decay_end, bump);
-  RK_LAUNCH_CHECK();
-  return RK_OK;
+  return sgd_launch<false>(w, wb, g, mom, n, lr, momentum, wd, nesterov, gscale, lr_ptr, decay_end, bump,
+                           GradClip<false>{}, stream);
+}
+
+extern "C" int rk_sgd_step_clip(float* w, void* wb, const float* g, float* mom, long long n, float lr, float momentum,
+                                float wd, int nesterov, float gscale, const float* lr_ptr, long long decay_end,
+                                int* bump, const double* partials, int nparts, float max_norm, float* stats,
+                                void* stream) {
+  GradClip<true> clip;
+  if (!clip_args(partials, nparts, max_norm, stats, clip)) return RK_EBADARG;
+  return sgd_launch<true>(w, wb, g, mom, n, lr, momentum, wd, nesterov, gscale, lr_ptr, decay_end, bump, clip,
+                          stream);
 }
 
 extern "C" int rk_adam_step(float* w, void* wb, const float* g, float* m, float* v, long long n, float lr, float b1,
                             float b2, float omb1, float omb2, float eps, float wd, int decoupled, float c1, float c2,
                             float gscale, const int* skip, const int* step_ptr, void* stream) {
-  if (n % 4) return RK_EUNSUPPORTED;
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4, 4096)), dim3(256), 0, (hipStream_t)stream, w, (bf16*)wb, g, m,
-                     v, n, lr, b1, b2, omb1, omb2, eps, wd, decoupled, c1, c2, gscale, skip, step_ptr);
+  return adam_launch<false>(w, wb, g, m, v, n, lr, b1, b2, omb1, omb2, eps, wd, decoupled, c1, c2, gscale, skip,
+                            step_ptr, GradClip<false>{}, stream);
+}
+
+extern "C" int rk_adam_step_clip(float* w, void* wb, const float* g, float* m, float* v, long long n, float lr,
+                                 float b1, float b2, float omb1, float omb2, float eps, float wd, int decoupled,
+                                 float c1, float c2, float gscale, const int* skip, const int* step_ptr,
+                                 const double* partials, int nparts, float max_norm, float* stats, void* stream) {
+  GradClip<true> clip;
+  if (!clip_args(partials, nparts, max_norm, stats, clip)) return RK_EBADARG;
+  return adam_launch<true>(w, wb, g, m, v, n, lr, b1, b2, omb1, omb2, eps, wd, decoupled, c1, c2, gscale, skip,
+                           step_ptr, clip, stream);
+}
+
+// partials[0 .. nparts) (fp64) = the block sums of g[0 .. n)^2; nparts must be the count the kernel's grid has for
+// n: min(256, ceil(n / 4 / 256)), at least 1 (ops/functional.py sumsq_parts)
+extern "C" int rk_grad_sumsq(const float* g, long long n, double* partials, int nparts, void* stream) {
+  if (n <= 0 || !g || !partials || nparts != sumsq_parts(n)) return RK_EBADARG;
+  if (n % 4 || (((unsigned long long)g) & 15)) return RK_EUNSUPPORTED;
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nparts), dim3(256), 0, (hipStream_t)stream, g, n, partials);
   RK_LAUNCH_CHECK();
   return RK_OK;
 }

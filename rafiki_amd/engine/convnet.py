@@ -47,7 +47,7 @@ import torch.nn.functional as TF
 from ..ops import f32 as S
 from ..ops import functional as F
 from ..ops.graphs import capture as _capture, device_sync as _device_sync
-from .flat import FlatAdam, FlatParams, FlatSGD, init_const, init_kaiming
+from .flat import FlatAdam, FlatParams, FlatSGD, check_clip_norm, init_const, init_kaiming
 
 VGG_SMALL_CFG = (64, 64, 'M', 128, 128, 'M', 256, 256, 'M', 512, 512, 'M')
 DTYPES = ('fp32', 'bf16')
@@ -123,7 +123,7 @@ class ConvNetEngine:
                  momentum: float = 0.9, weight_decay: float = 5e-4, nesterov: bool = True,
                  betas=(0.9, 0.999), input_bn: bool = False, dtype: Optional[str] = None, bn: bool = True,
                  augment: Optional[dict] = None, mix: Optional[dict] = None, label_smoothing: float = 0.0,
-                 dropout: float = 0.0, feature_dropout: float = 0.0):
+                 dropout: float = 0.0, feature_dropout: float = 0.0, clip_norm: Optional[float] = None):
         self.device = torch.device(device)
         self.dtype = dtype or default_dtype()
         if self.dtype not in DTYPES:
@@ -190,6 +190,10 @@ class ConvNetEngine:
         if self.feature_dropout > 0.0 and self.flat_input:
             raise ValueError('feature_dropout needs conv features; a flat-input net reads the caller\'s buffer')
         self._drops = self.dropout > 0.0 or self.feature_dropout > 0.0
+        # clip_norm: the cap on the global norm of the step's gradients (inf: only measured, see grad_stats) — one
+        # fp64 sum-of-squares launch over the gradient arena, then the optimizer's launch reads the coefficient
+        # on the device, so it lives inside the captured step.  None adds no launch and no buffer
+        self.clip_norm = check_clip_norm(clip_norm)
         self._drop_at = [0, 0]                        # (epoch, step within it) of the next step: the CPU path
         self._drop_step = self._drop_step_src = None  # device step word; the scheduled graph reads _ctr instead
         self._dropped = {}                            # keep_dropped: site -> the tensor last dropped in the forward
@@ -258,9 +262,11 @@ class ConvNetEngine:
             for b in self.blocks]
         self._ones = None if self.bn else torch.ones(max([b[2] for b in self.blocks] or [1]), device=self.device)
         if optimizer == 'adam':
-            self.opt = FlatAdam(self.flat, lr, betas=betas, weight_decay=weight_decay, decoupled=True)
+            self.opt = FlatAdam(self.flat, lr, betas=betas, weight_decay=weight_decay, decoupled=True,
+                                clip_norm=self.clip_norm)
         else:
-            self.opt = FlatSGD(self.flat, lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
+            self.opt = FlatSGD(self.flat, lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov,
+                               clip_norm=self.clip_norm)
         self.loss_sum = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.correct = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.seen = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -336,6 +342,16 @@ class ConvNetEngine:
         self.loss_sum.zero_()
         self.correct.zero_()
         self.seen.zero_()
+        if self.opt is not None and self.opt.clip is not None:
+            self.opt.clip.reset()
+
+    def grad_stats(self) -> dict:
+        """The gradient norms of the training steps since reset_metrics() (one host sync): 'last_norm', 'mean_norm'
+        and 'max_norm' (over the steps with a finite norm), and the counts 'clipped' (scaled down), 'skipped'
+        (norm not finite: nothing updated) and 'steps'.  Needs clip_norm (inf to measure only)."""
+        if self.opt is None or self.opt.clip is None:
+            raise RuntimeError('grad_stats needs clip_norm (float(\'inf\') measures without clipping)')
+        return self.opt.clip.read()
 
     # ----------------------------------------------------------------------------- GPU train
     def _train_step_gpu(self, x, labels):
@@ -804,7 +820,7 @@ class ConvNetEngine:
         # warm the allocator / library outside capture; these steps use zero inputs and are
         # undone by restoring the parameter state afterwards.
         snap = [self.flat.master.clone(), self.running.clone()]
-        opt_state = [t.clone() for t in self._opt_tensors()]
+        opt_state = [t.clone() for t in self._warmup_tensors()]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -818,7 +834,7 @@ class ConvNetEngine:
         self.flat.master.copy_(snap[0])
         self.flat.sync_bf16()
         self.running.copy_(snap[1])
-        for t, v in zip(self._opt_tensors(), opt_state):
+        for t, v in zip(self._warmup_tensors(), opt_state):
             t.copy_(v)
         self.reset_metrics()
         self._graph, self._graph_batch = g, batch_size
@@ -881,7 +897,7 @@ class ConvNetEngine:
                     self.opt.bump = None
 
         snap = [self.flat.master.clone(), self.running.clone()]
-        opt_state = [t.clone() for t in self._opt_tensors()]
+        opt_state = [t.clone() for t in self._warmup_tensors()]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -895,7 +911,7 @@ class ConvNetEngine:
         self.flat.master.copy_(snap[0])
         self.flat.sync_bf16()
         self.running.copy_(snap[1])
-        for t, v in zip(self._opt_tensors(), opt_state):
+        for t, v in zip(self._warmup_tensors(), opt_state):
             t.copy_(v)
         self._ctr.zero_()
         self.reset_metrics()
@@ -1062,6 +1078,10 @@ class ConvNetEngine:
         if isinstance(o, FlatAdam):
             return [o.m, o.v, o.t]
         return [o.mom] if o.mom is not None else []
+
+    def _warmup_tensors(self):
+        """What a capture's warm-up steps must leave as they found it: the optimizer state and the clip stats."""
+        return self._opt_tensors() + ([] if self.opt.clip is None else [self.opt.clip.stats])
 
     def step_graph(self, x, labels):
         """Copy a batch into the static buffers and replay the captured step."""

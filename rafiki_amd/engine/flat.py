@@ -185,12 +185,73 @@ class FlatParams:
         self.sync_bf16()
 
 
-class FlatSGD:
-    """SGD (+momentum, +nesterov, decoupled-range weight decay) over a FlatParams arena."""
+def check_clip_norm(clip_norm) -> Optional[float]:
+    """``clip_norm`` as the optimizers and engines take it: None (off) or a number > 0 — the cap on the global
+    gradient norm, ``float('inf')`` to measure the norm without clipping.  Anything else raises ValueError."""
+    if clip_norm is None:
+        return None
+    if isinstance(clip_norm, bool) or not isinstance(clip_norm, (int, float)) or not clip_norm > 0:
+        raise ValueError('clip_norm must be None or a number > 0 (inf: measure only), got {!r}'.format(clip_norm))
+    return float(clip_norm)
 
-    def __init__(self, flat: FlatParams, lr, momentum=0.9, weight_decay=5e-4, nesterov=True):
+
+class GradClip:
+    """Global-norm gradient clipping of one fp32 gradient arena, on its device: the fp64 partial sums of squares
+    (ops grad_sumsq), the cap and the 8-float stats block the optimizer launch updates.  Both buffers are made
+    here, never inside a graph capture.  On the CPU ``coef`` is the host statement of the kernels' arithmetic."""
+
+    def __init__(self, grad: torch.Tensor, max_norm: float):
+        self.max_norm = check_clip_norm(max_norm)
+        assert self.max_norm is not None
+        self.partials = torch.zeros(F.sumsq_parts(grad.numel()), dtype=torch.float64, device=grad.device)
+        self.stats = torch.zeros(F.CLIP_STATS, dtype=torch.float32, device=grad.device)
+
+    def reduce(self, grad):
+        """Launch the sum of squares of ``grad`` (the whole arena) and return the optimizer's ``clip=`` argument."""
+        F.grad_sumsq(grad, self.partials)
+        return (self.partials, self.max_norm, self.stats)
+
+    def coef(self, grad) -> Optional[torch.Tensor]:
+        """CPU path: the fp32 coefficient min(1, max_norm / (norm + 1e-6)) of ``grad``, norm = the fp32 rounding
+        of the square root of the fp64 sum of squares; None when the norm is not finite (the step is skipped).
+        Updates the stats as the kernel does."""
+        norm = grad.double().pow(2).sum().sqrt().float()
+        st = self.stats
+        st[0] = norm
+        st[6] += 1
+        if not bool(torch.isfinite(norm)):
+            st[1] = 0.0
+            st[5] += 1
+            return None
+        coef = torch.clamp(torch.tensor(self.max_norm, dtype=torch.float32) / (norm + torch.tensor(1e-6)), max=1.0)
+        st[1] = coef
+        st[2] += norm
+        st[3] = torch.maximum(st[3], norm)
+        if bool(coef < 1.0):
+            st[4] += 1
+        return coef
+
+    def read(self) -> dict:
+        """The stats since the last reset (one host sync): the norm of the last step, the mean and the maximum of
+        the finite norms, and the counts of clipped (coef < 1), skipped (non-finite norm) and all steps."""
+        st = self.stats.tolist()
+        finite = st[6] - st[5]
+        return {'last_norm': st[0], 'mean_norm': st[2] / finite if finite > 0 else 0.0, 'max_norm': st[3],
+                'clipped': int(st[4]), 'skipped': int(st[5]), 'steps': int(st[6])}
+
+    def reset(self):
+        self.stats.zero_()
+
+
+class FlatSGD:
+    """SGD (+momentum, +nesterov, decoupled-range weight decay) over a FlatParams arena.  ``clip_norm``: see
+    check_clip_norm; the gradients are scaled by min(1, clip_norm / (norm + 1e-6)) inside the step's launch, and a
+    step whose norm is not finite changes nothing."""
+
+    def __init__(self, flat: FlatParams, lr, momentum=0.9, weight_decay=5e-4, nesterov=True, clip_norm=None):
         self.flat, self.lr, self.momentum, self.wd, self.nesterov = flat, float(lr), float(momentum), float(
             weight_decay), bool(nesterov)
+        self.clip = None if check_clip_norm(clip_norm) is None else GradClip(flat.grad, clip_norm)
         self.mom = torch.zeros_like(flat.master) if momentum > 0 else None
         # device-side LR multiplier: schedules change it without re-capturing the graph
         self.lr_scale = torch.ones(1, dtype=torch.float32, device=flat.device)
@@ -202,13 +263,20 @@ class FlatSGD:
             # one launch: decayed parameters come first in the arena, wd applies below decay_end
             F.sgd_step(f.master, f.grad, self.mom, wb=f.bf16, lr=self.lr, momentum=self.momentum,
                        weight_decay=self.wd, nesterov=self.nesterov, lr_tensor=self.lr_scale,
-                       decay_end=f.decay_end, bump=self.bump)
+                       decay_end=f.decay_end, bump=self.bump,
+                       clip=None if self.clip is None else self.clip.reduce(f.grad))
             return
         # CPU reference path (same math as sgd_kernel)
+        grad = f.grad
+        if self.clip is not None:
+            coef = self.clip.coef(grad)
+            if coef is None:
+                return
+            grad = grad * coef
         lr = self.lr * float(self.lr_scale.item())
         wd = torch.zeros_like(f.master)
         wd[:f.decay_end] = self.wd
-        g = f.grad + wd * f.master
+        g = grad + wd * f.master
         if self.mom is not None:
             self.mom.mul_(self.momentum).add_(g)
             d = g + self.momentum * self.mom if self.nesterov else self.mom
@@ -222,15 +290,19 @@ class FlatSGD:
 
 
 class FlatAdam:
-    """Adam / AdamW over a FlatParams arena; step counter lives on the device (graph-safe)."""
+    """Adam / AdamW over a FlatParams arena; step counter lives on the device (graph-safe).  ``clip_norm``: as for
+    FlatSGD, whole-arena steps only; a skipped step still counts in the step counter, as one skipped by
+    ``skip_flag`` does on the GPU."""
 
-    def __init__(self, flat: FlatParams, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False):
+    def __init__(self, flat: FlatParams, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False,
+                 clip_norm=None):
         self.flat, self.lr, self.b1, self.b2, self.eps = flat, float(lr), float(betas[0]), float(betas[1]), float(eps)
         self.wd, self.decoupled = float(weight_decay), bool(decoupled)
         self.m = torch.zeros_like(flat.master)
         self.v = torch.zeros_like(flat.master)
         self.t = torch.zeros(1, dtype=torch.int32, device=flat.device)
         self.skip_flag: Optional[torch.Tensor] = None
+        self.clip = None if check_clip_norm(clip_norm) is None else GradClip(flat.grad, clip_norm)
 
     def reset_state(self):
         self.m.zero_()
@@ -245,6 +317,8 @@ class FlatAdam:
         another int32 device counter to advance in the same launch when the step runs as one
         multi-segment launch; returns True when it did (the caller advances it otherwise)."""
         f = self.flat
+        if self.clip is not None and live is not None:
+            raise NotImplementedError('clip_norm clips the whole arena\'s norm: no live ranges')
         # Equalized LR (pg_gans.py:1006-1013) is applied by re-parameterisation: the arena holds the
         # EFFECTIVE weights c*w, stepped with lr*c and eps*c — algebraically identical to Adam on w.
         segs = f.segments(self.wd)
@@ -266,22 +340,33 @@ class FlatAdam:
                     F.adam_multi(f.master, f.grad, self.m, self.v, tab, wb=f.bf16, beta1=self.b1, beta2=self.b2,
                                  decoupled=self.decoupled, step_tensor=self.t, skip_flag=self.skip_flag, bump=bump)
                     return bump is not None
+            # one reduce over the whole arena; every segment's launch folds the same partials, the first one
+            # also writes the stats
+            clip = None if self.clip is None else self.clip.reduce(f.grad)
             for a, b, wd, mult in segs:
                 if b > a:
                     F.adam_step(f.master[a:b], f.grad[a:b], self.m[a:b], self.v[a:b],
                                 wb=None if f.bf16 is None else f.bf16[a:b],
                                 lr=self.lr * mult, beta1=self.b1, beta2=self.b2, eps=self.eps * mult,
                                 weight_decay=wd, decoupled=self.decoupled, step_tensor=self.t,
-                                skip_flag=self.skip_flag)
+                                skip_flag=self.skip_flag, clip=clip)
+                    clip = None if clip is None else clip[:2] + (None,)
             return
         if self.skip_flag is not None and int(self.skip_flag.item()) != 0:
             return
         self.t += 1
+        coef = None
+        if self.clip is not None:
+            coef = self.clip.coef(f.grad)
+            if coef is None:
+                return
         t = int(self.t.item())
         c1 = 1.0 / (1.0 - self.b1 ** t) if self.b1 > 0 else 1.0
         c2 = 1.0 / (1.0 - self.b2 ** t)
         for a, b, wd, mult in segs:
             w, gr, m, v = f.master[a:b], f.grad[a:b], self.m[a:b], self.v[a:b]
+            if coef is not None:
+                gr = gr * coef
             g = gr if self.decoupled else gr + wd * w
             m.mul_(self.b1).add_((1 - self.b1) * g)
             v.mul_(self.b2).add_((1 - self.b2) * g * g)

@@ -36,6 +36,7 @@ from ..ops import _lib
 from ..ops import f32 as S
 from ..ops import graphs
 from ..ops.functional import _p, _s
+from .flat import GradClip, check_clip_norm
 
 IGNORE = -100
 _DROP_STREAM = 0x7a67   # Philox stream id of the tagger's dropout
@@ -82,9 +83,12 @@ def pack_batch(x_bl: np.ndarray, y_bl, padding_idx: int = 0, vocab: Optional[int
 
 class TaggerEngine:
     """Flat padded parameters + Adam state of one PyBiLstm ``Net`` (attributes emb, lstm, out), and its
-    training step on the in-tree kernels.  ``step`` takes batch-first numpy ids / labels."""
+    training step on the in-tree kernels.  ``step`` takes batch-first numpy ids / labels.  ``clip_norm`` (None: off;
+    > 0: the cap on the global gradient norm; inf: measure only): one sum-of-squares launch over the gradient arena
+    right before the Adam launch, which reads the coefficient on the device — both inside the step's graph."""
 
-    def __init__(self, net, lr: float, dropout: float, *, seed: int = 0, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, net, lr: float, dropout: float, *, seed: int = 0, betas=(0.9, 0.999), eps=1e-8,
+                 clip_norm: Optional[float] = None):
         dev = net.emb.weight.device
         assert dev.type == 'cuda', 'TaggerEngine runs on the GPU kernels'
         V, E = net.emb.weight.shape
@@ -107,6 +111,7 @@ class TaggerEngine:
         self.w, self.g, self.m, self.v = (torch.zeros(o, **f) for _ in range(4))
         self.ctr = torch.zeros(4, device=dev, dtype=torch.int32)       # [0]: steps taken (Adam t, dropout)
         self.loss_sum = torch.zeros(4, **f)                              # [0]: sum of batch-mean losses
+        self.clip = None if check_clip_norm(clip_norm) is None else GradClip(self.g, clip_norm)
         self.whhT = torch.empty((2, HP, 4 * HP), **f)
         self.bsum = torch.empty(8 * HP, **f)
         self.lr, self.p, self.seed = float(lr), float(dropout), int(seed) & ((1 << 63) - 1)
@@ -218,8 +223,13 @@ class TaggerEngine:
                   self.V, s)
         if update:
             b1, b2 = self.betas
-            _lib.call("rk_adam_step", _p(self.w), None, _p(self.g), _p(self.m), _p(self.v), self.numel, self.lr, b1, b2,
-                      1.0 - b1, 1.0 - b2, self.eps, 0.0, 0, 1.0, 1.0, 1.0, None, _p(self.ctr), s)
+            adam = (_p(self.w), None, _p(self.g), _p(self.m), _p(self.v), self.numel, self.lr, b1, b2, 1.0 - b1,
+                    1.0 - b2, self.eps, 0.0, 0, 1.0, 1.0, 1.0, None, _p(self.ctr))
+            if self.clip is None:
+                _lib.call("rk_adam_step", *adam, s)
+            else:
+                partials, max_norm, stats = self.clip.reduce(self.g)
+                _lib.call("rk_adam_step_clip", *adam, _p(partials), partials.numel(), max_norm, _p(stats), s)
 
     def _upload(self, words: np.ndarray, key) -> torch.Tensor:
         """Async copy of a packed batch into the shape's device input buffer (pinned, double-buffered)."""
@@ -263,10 +273,19 @@ class TaggerEngine:
                 self._graphs[key] = cg
 
     def take_loss(self) -> float:
-        """Sum of the batch-mean losses since the last call (one host sync)."""
+        """Sum of the batch-mean losses since the last call (one host sync); also restarts the gradient-norm
+        stats, so read grad_stats() first."""
         v = float(self.loss_sum[0].item())
         _lib.call("rk_zero32", _p(self.loss_sum), 4, _s())
+        if self.clip is not None:
+            self.clip.reset()
         return v
+
+    def grad_stats(self) -> dict:
+        """The gradient norms of the steps since the last take_loss() (one host sync): see GradClip.read."""
+        if self.clip is None:
+            raise RuntimeError('grad_stats needs clip_norm (float(\'inf\') measures without clipping)')
+        return self.clip.read()
 
     # ------------------------------------------------------------------------ inference
     @torch.no_grad()

@@ -74,7 +74,9 @@ class NativeImageClassifier(BaseModel):
         'none'), ``mix_alpha`` (the Beta parameter, default 1.0), ``mix_prob`` (the share of mixed steps, default 1.0
         for mixup and 0.5 for cutmix) and ``label_smoothing`` (default 0.0); and its ``dropout`` (every FC hidden
         layer's output) and ``feature_dropout`` (the flattened conv features) rates from the knobs of those names
-        (default 0.0, each in [0, 1)), passed on only when non-zero.  Training only."""
+        (default 0.0, each in [0, 1)), passed on only when non-zero; and its ``clip_norm`` from the knobs
+        ``clip_norm`` (the cap on the global gradient norm, default 0 = off) and ``track_grad_norm`` (default False;
+        True without a cap passes inf: the norm is measured and logged, never clipped).  Training only."""
         mode = self._knobs.get('mix', 'none')
         if mode not in self.MIX_MODES:
             raise ValueError('mix must be one of {}, got {!r}'.format(self.MIX_MODES, mode))
@@ -90,6 +92,13 @@ class NativeImageClassifier(BaseModel):
                 raise ValueError('{} must lie in [0, 1), got {!r}'.format(name, self._knobs[name]))
             if rate != 0.0:
                 out[name] = rate
+        cap = float(self._knobs.get('clip_norm', 0.0))
+        if not 0.0 <= cap < math.inf:
+            raise ValueError('clip_norm must be 0 (off) or a finite cap > 0, got {!r}'.format(self._knobs['clip_norm']))
+        if cap != 0.0:
+            out['clip_norm'] = cap
+        elif bool(self._knobs.get('track_grad_norm', False)):
+            out['clip_norm'] = math.inf
         return out
 
     def _build(self, num_classes, channels, dtype=None, augment=None, **regularisers):
@@ -141,6 +150,8 @@ class NativeImageClassifier(BaseModel):
         logger.define_loss_plot()
         logger.define_plot('Train accuracy', ['train_acc'], x_axis='epoch')
         logger.define_plot('Throughput', ['images_per_sec'], x_axis='epoch')
+        if eng.clip_norm is not None:
+            logger.define_plot('Gradient norm', ['grad_norm', 'grad_norm_max', 'clipped_share'], x_axis='epoch')
         sched = self._knobs.get('lr_schedule', 'cosine')
         ctx = trial_context()
         ck = ctx.checkpoint
@@ -198,6 +209,10 @@ class NativeImageClassifier(BaseModel):
             logger.log_loss(loss=float(eng.loss_sum.item()) / seen, epoch=epoch)
             logger.log(train_acc=float(eng.correct.item()) / seen, epoch=epoch)
             logger.log(images_per_sec=done * bs / dt, epoch=epoch)
+            if eng.clip_norm is not None:   # read at the epoch's sync above; reset_metrics() restarts them
+                gs = eng.grad_stats()
+                logger.log(grad_norm=gs['mean_norm'], grad_norm_max=gs['max_norm'],
+                           clipped_share=gs['clipped'] / max(1, gs['steps']), epoch=epoch)
             if ck is not None and ck.due(epoch) and step < total:
                 ck.save(self._ckpt_state(step, gen), epoch)
             faults.maybe_fail('crash', epoch=epoch, rank=ctx.rank)

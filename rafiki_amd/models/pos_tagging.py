@@ -8,7 +8,10 @@ Differences: Viterbi runs vectorised in numpy log-space; the BiLSTM applies cros
 logits (the reference applies it to softmax outputs, bug (k)) and batches sentences bucketed by
 length.  On a GPU the BiLSTM's training step and prediction run on the native tagger engine
 (engine/tagger.py: in-tree kernels only, one hipGraph per bucket shape, any knob value); on the CPU
-the same network runs as torch modules.
+the same network runs as torch modules.  ``clip_norm`` (a knob read by PyBiLstm, default 0 = off, and searched by
+PyBiLstmClip) caps the global gradient norm of every step: on the device inside the step's graph on the GPU, by
+torch's clip_grad_norm_ on the CPU; either way the trial logs the epoch's mean and largest norm and the share of
+clipped steps.
 """
 import math
 
@@ -138,6 +141,13 @@ class PyBiLstm(BaseModel):
         self._tag_count = 0
         self.device = trial_context().device
 
+    def _clip_norm(self):
+        """The knob ``clip_norm``: None when 0 (off), else the finite cap > 0."""
+        cap = float(self._knobs.get('clip_norm', 0.0))
+        if not 0.0 <= cap < math.inf:
+            raise ValueError('clip_norm must be 0 (off) or a finite cap > 0, got {!r}'.format(self._knobs['clip_norm']))
+        return cap if cap != 0.0 else None
+
     def _create(self):
         import torch
         import torch.nn as nn
@@ -211,6 +221,9 @@ class PyBiLstm(BaseModel):
         tags = [[t[1] for t in s] for s in sents]
         rng = np.random.default_rng(0)
         logger.define_loss_plot()
+        clip = self._clip_norm()
+        if clip is not None:
+            logger.define_plot('Gradient norm', ['grad_norm', 'grad_norm_max', 'clipped_share'], x_axis='epoch')
         epochs = int(self._knobs.get('epochs', 10))
         ck = trial_context().checkpoint
         saved = ck.load() if ck is not None else None
@@ -226,15 +239,22 @@ class PyBiLstm(BaseModel):
             self._net.train()
             tot = torch.zeros((), device=self.device)
             n = 0
+            norms = []
             for _, x, y in self._batches(ids, tags, int(self._knobs.get('batch_size', 32)), True, rng):
                 logits = self._net(x)
                 loss = F.cross_entropy(logits.reshape(-1, self._tag_count), y.reshape(-1), ignore_index=-100)
                 opt.zero_grad()
                 loss.backward()
+                if clip is not None:
+                    norms.append(torch.nn.utils.clip_grad_norm_(self._net.parameters(), clip).detach())
                 opt.step()
                 tot += loss.detach()   # summed on the device: one host sync per epoch
                 n += 1
             logger.log_loss(loss=float(tot.item()) / max(1, n), epoch=ep)
+            if clip is not None and norms:
+                nv = torch.stack(norms).float()
+                logger.log(grad_norm=float(nv.mean()), grad_norm_max=float(nv.max()),
+                           clipped_share=float((nv > clip).float().mean()), epoch=ep)
             if ck is not None and ck.due(ep) and ep + 1 < epochs:
                 ck.save(self._ckpt_state(opt, rng), ep)
             faults.maybe_fail('crash', epoch=ep, rank=0)
@@ -244,7 +264,8 @@ class PyBiLstm(BaseModel):
         engine's Philox stream (seeded from the trial's numpy generator), one graph per bucket shape."""
         from rafiki_amd.engine.tagger import TaggerEngine
         eng = TaggerEngine(self._net, float(self._knobs.get('learning_rate', 0.05)),
-                           float(self._knobs.get('word_dropout', 0.1)), seed=int(rng.integers(1 << 62)))
+                           float(self._knobs.get('word_dropout', 0.1)), seed=int(rng.integers(1 << 62)),
+                           clip_norm=self._clip_norm())
         start = 0
         if saved is not None:
             st = saved['state']
@@ -263,7 +284,11 @@ class PyBiLstm(BaseModel):
             for _, x, y in self._batches_np(ids, tags, bs, True, rng):
                 eng.step(x, y)
                 n += 1
+            gs = eng.grad_stats() if eng.clip is not None else None   # before take_loss() restarts them
             logger.log_loss(loss=eng.take_loss() / max(1, n), epoch=ep)   # one host sync per epoch
+            if gs is not None:
+                logger.log(grad_norm=gs['mean_norm'], grad_norm_max=gs['max_norm'],
+                           clipped_share=gs['clipped'] / max(1, gs['steps']), epoch=ep)
             if ck is not None and ck.due(ep) and ep + 1 < epochs:
                 eng.store_module(self._net)
                 ck.save({'engine': eng.state(), 'np_rng': rng.bit_generator.state,
@@ -333,3 +358,14 @@ class PyBiLstm(BaseModel):
         self._net = self._create()
         self._net.load_state_dict(params['net_state_dict'])
         self._engine = None
+
+
+class PyBiLstmClip(PyBiLstm):
+    """PyBiLstm with the cap on the global gradient norm in the search space (Adam at learning rates up to 0.1 on
+    an LSTM is what clipping is for)."""
+
+    @staticmethod
+    def get_knob_config():
+        cfg = PyBiLstm.get_knob_config()
+        cfg['clip_norm'] = FloatKnob(0.25, 8.0, is_exp=True)
+        return cfg

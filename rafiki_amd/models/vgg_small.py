@@ -75,6 +75,19 @@ class VggSmallDrop(VggSmallReg):
         return cfg
 
 
+class VggSmallClip(VggSmallDrop):
+    """VggSmallDrop with the cap on the global gradient norm in the search space: ``clip_norm`` scales a step's
+    gradients by min(1, clip_norm / norm), the norm summed and the coefficient applied on the device inside the
+    step graph (``ConvNetEngine(clip_norm=...)``); the trial logs the epoch's mean and largest norm and the share
+    of clipped steps."""
+
+    @staticmethod
+    def get_knob_config():
+        cfg = VggSmallDrop.get_knob_config()
+        cfg['clip_norm'] = FloatKnob(0.5, 10.0, is_exp=True)
+        return cfg
+
+
 class VggSmallTrial(VggSmall):
     """The benchmark's trial definition (bench.py phase 2): VggSmall at full width, batch 256, ten
     epochs over a CIFAR-sized train split (50k images), evaluated on 10k, parameters pickled — a

@@ -52,6 +52,11 @@ _SIGS = {
     "rk_softmax_xent_soft": [vp, i32, vp, vp, vp, f32, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp],
     "rk_sgd_step": [vp, vp, vp, vp, i64, f32, f32, f32, i32, f32, vp, i64, vp, vp],
     "rk_adam_step": [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, i32, f32, f32, f32, vp, vp, vp],
+    # the same two with the clip coefficient read on the device: + (partials, nparts, max_norm, stats)
+    "rk_sgd_step_clip": [vp, vp, vp, vp, i64, f32, f32, f32, i32, f32, vp, i64, vp, vp, i32, f32, vp, vp],
+    "rk_adam_step_clip": [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, i32, f32, f32, f32, vp, vp, vp,
+                          i32, f32, vp, vp],
+    "rk_grad_sumsq": [vp, i64, vp, i32, vp],
     "rk_add_int": [vp, i32, vp],
     "rk_rows_reduce": [vp, i32, i64, i32, vp, vp],
     "rk_fold_rows": [vp, i32, i64, vp, i32, f32, vp],

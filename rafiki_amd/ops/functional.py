@@ -732,25 +732,65 @@ def softmax_xent_soft(logits, labels, ncls, *, labels2=None, lam=None, eps=0.0, 
               _p(loss_sum), _p(correct), _p(counted), _s())
 
 
+CLIP_STATS = 8   # floats of a clip stats block: last norm, last coef, sum / max of finite norms, clipped, skipped, steps
+
+
+def sumsq_parts(n: int) -> int:
+    """The number of fp64 partial sums ``grad_sumsq`` writes for n elements: a function of n alone (at most 256),
+    so the summation order does not depend on the device."""
+    return min(256, max(1, (n // 4 + 255) // 256))
+
+
+def grad_sumsq(g, partials):
+    """partials [sumsq_parts(g.numel())] float64 = block sums of g^2 (fp32, numel % 4 == 0), squares and sums in
+    fp64 in a fixed order: two launches on the same gradients give the same bits.  Their sum is the squared global
+    norm the ``clip=`` form of sgd_step / adam_step folds on the device."""
+    n = g.numel()
+    if g.dtype != torch.float32 or not g.is_contiguous() or partials.dtype != torch.float64 or \
+            partials.numel() != sumsq_parts(n):
+        raise ValueError('grad_sumsq: contiguous float32 gradients and float64 partials [sumsq_parts(n)]')
+    _lib.call("rk_grad_sumsq", _p(g), n, _p(partials), partials.numel(), _s())
+    return partials
+
+
+def _clip_args(clip):
+    """``clip`` = (partials, max_norm, stats): the partials of grad_sumsq over the WHOLE gradient arena, the norm
+    cap (> 0; inf: measure only) and the float32 [CLIP_STATS] block the launch updates (None: leave it)."""
+    partials, max_norm, stats = clip
+    if partials.dtype != torch.float64 or (stats is not None and (stats.dtype != torch.float32 or
+                                                                  stats.numel() < CLIP_STATS)):
+        raise ValueError('clip: float64 partials and a float32 [{}] stats block'.format(CLIP_STATS))
+    return _p(partials), partials.numel(), float(max_norm), _p(stats)
+
+
 def sgd_step(w, g, mom=None, *, wb=None, lr, momentum=0.0, weight_decay=0.0, nesterov=False, grad_scale=1.0,
-             lr_tensor=None, decay_end=None, bump=None):
+             lr_tensor=None, decay_end=None, bump=None, clip=None):
     """Fused SGD over a flat range; ``weight_decay`` applies to elements [0, decay_end) (default: all).
-    ``bump``: int32 device counter incremented once by the launch (graph-step counters)."""
+    ``bump``: int32 device counter incremented once by the launch (graph-step counters).  ``clip`` (see
+    _clip_args): the launch scales the gradients by grad_scale * min(1, max_norm / (norm + 1e-6)), the norm read
+    from the partials on the device, and leaves every buffer untouched when the norm is not finite."""
     n = w.numel()
-    _lib.call("rk_sgd_step", _p(w), _p(wb), _p(g), _p(mom), n, float(lr), float(momentum),
-              float(weight_decay), int(nesterov), float(grad_scale), _p(lr_tensor), n if decay_end is None else
-              int(decay_end), _p(bump), _s())
+    args = (_p(w), _p(wb), _p(g), _p(mom), n, float(lr), float(momentum), float(weight_decay), int(nesterov),
+            float(grad_scale), _p(lr_tensor), n if decay_end is None else int(decay_end), _p(bump))
+    if clip is None:
+        _lib.call("rk_sgd_step", *args, _s())
+    else:
+        _lib.call("rk_sgd_step_clip", *args, *_clip_args(clip), _s())
 
 
 def adam_step(w, g, m, v, *, wb=None, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, decoupled=False,
-              step=1, grad_scale=1.0, skip_flag=None, step_tensor=None):
+              step=1, grad_scale=1.0, skip_flag=None, step_tensor=None, clip=None):
     """Adam/AdamW.  ``step_tensor`` (device int32, already incremented) overrides ``step`` so the
-    bias corrections stay right under hipGraph replay."""
+    bias corrections stay right under hipGraph replay.  ``clip``: as for sgd_step."""
     c1 = 1.0 / (1.0 - beta1 ** step) if beta1 > 0 else 1.0
     c2 = 1.0 / (1.0 - beta2 ** step)
-    _lib.call("rk_adam_step", _p(w), _p(wb), _p(g), _p(m), _p(v), w.numel(), float(lr), float(beta1), float(beta2),
-              1.0 - float(beta1), 1.0 - float(beta2), float(eps), float(weight_decay), int(decoupled), float(c1),
-              float(c2), float(grad_scale), _p(skip_flag), _p(step_tensor), _s())
+    args = (_p(w), _p(wb), _p(g), _p(m), _p(v), w.numel(), float(lr), float(beta1), float(beta2),
+            1.0 - float(beta1), 1.0 - float(beta2), float(eps), float(weight_decay), int(decoupled), float(c1),
+            float(c2), float(grad_scale), _p(skip_flag), _p(step_tensor))
+    if clip is None:
+        _lib.call("rk_adam_step", *args, _s())
+    else:
+        _lib.call("rk_adam_step_clip", *args, *_clip_args(clip), _s())
 
 
 # ---- multi-segment updates (one launch over a set of arena ranges; loss_optim.hip adam_multi_kernel)
