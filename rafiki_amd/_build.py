@@ -32,6 +32,8 @@ PYLIST_LIB = NATIVE_DIR / "librafiki_pylist.so"
 ARCH = os.environ.get("RAFIKI_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result"]
+# extra hipcc flags of single translation units (by stem): crf.hip is built without the packed-fp32 instructions
+FILE_FLAGS = {"crf": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 CXX = os.environ.get("CXX", "g++")
 CXX_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-pthread"]
 
@@ -64,7 +66,7 @@ def build_kernels(verbose: bool = False, jobs: int | None = None) -> Path:
         o = OBJ_DIR / (s.stem + ".o")
         objs.append(o)
         if _stale(o, [s, *headers]):
-            cmds.append([HIPCC, *HIP_FLAGS, "-c", s, "-o", o])
+            cmds.append([HIPCC, *HIP_FLAGS, *FILE_FLAGS.get(s.stem, []), "-c", s, "-o", o])
     n = jobs or min(8, os.cpu_count() or 4)
     with cf.ThreadPoolExecutor(max_workers=max(1, n)) as ex:
         for f in [ex.submit(_run, c, verbose) for c in cmds]:

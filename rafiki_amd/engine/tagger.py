@@ -24,6 +24,12 @@ labels, the embedding-gradient runs and 1/#tokens into one int32 buffer and send
 async copy from pinned memory (double-buffered, so packing batch k+1 overlaps step k on the GPU).
 The device step counter drives both Adam's bias corrections and the dropout stream, so replays draw
 fresh masks.
+
+A net with a ``crf`` attribute (ops/crf.py: PyBiLstmCrf) trains on the linear-chain CRF's sentence-level loss
+instead: ``crf_trans`` / ``crf_start`` / ``crf_end`` follow ``b_out`` in the arena, ``rk_crf_nll`` (crf.hip) takes
+the place of the softmax cross-entropy and writes d(logits) and the three CRF gradients, the batch carries its
+sentence lengths, and ``decode`` runs Viterbi on the eval logits.  Without one, the arena layout, the launches and
+the captured graphs are the softmax step's.
 """
 from __future__ import annotations
 
@@ -46,13 +52,14 @@ def _cdiv(a: int, b: int) -> int:
     return -(-a // b)
 
 
-def pack_batch(x_bl: np.ndarray, y_bl, padding_idx: int = 0, vocab: Optional[int] = None) -> np.ndarray:
+def pack_batch(x_bl: np.ndarray, y_bl, padding_idx: int = 0, vocab: Optional[int] = None, lens=None) -> np.ndarray:
     """One batch as the int32 words the step reads: x_bl / y_bl are [B, L] (batch-first, like the
     reference's batches; labels IGNORE where no token).  Layout, with n = L*B tokens in time-major
     order (t, b): [ids n | labels n | perm n | run ids n | run starts n+1 | #runs | 1/#labelled as
     float bits].  perm is the stable argsort of the ids; run u covers perm[start[u]:start[u+1]] and
     has id uniq[u] (-1 for the padding id: no gradient).  With ``vocab``, ids outside [0, vocab) become
-    the padding id, as the forward's gather treats them (no gradient row is written for them)."""
+    the padding id, as the forward's gather treats them (no gradient row is written for them).  With ``lens``
+    ([B] sentence lengths, read by the CRF step) B more words follow; without, the layout is as above."""
     B, L = x_bl.shape
     n = B * L
     ids = np.ascontiguousarray(x_bl.T, dtype=np.int32).reshape(-1)
@@ -70,7 +77,7 @@ def pack_batch(x_bl: np.ndarray, y_bl, padding_idx: int = 0, vocab: Optional[int
     uniq[uniq == padding_idx] = -1
     U = len(uniq)
     cnt = int((labels != IGNORE).sum())
-    out = np.zeros(5 * n + 3, np.int32)
+    out = np.zeros(5 * n + 3 + (0 if lens is None else B), np.int32)
     out[0:n] = ids
     out[n:2 * n] = labels
     out[2 * n:3 * n] = perm
@@ -78,6 +85,8 @@ def pack_batch(x_bl: np.ndarray, y_bl, padding_idx: int = 0, vocab: Optional[int
     out[4 * n:4 * n + U + 1] = starts
     out[5 * n + 1] = U
     out[5 * n + 2:5 * n + 3] = np.array([1.0 / max(1, cnt)], np.float32).view(np.int32)
+    if lens is not None:
+        out[5 * n + 3:] = lens
     return out
 
 
@@ -96,12 +105,17 @@ class TaggerEngine:
         NT = net.out.out_features
         if H > 128 or net.lstm.num_layers != 1 or not net.lstm.bidirectional:
             raise ValueError('TaggerEngine: one bidirectional layer of hidden <= 128 (got {})'.format(H))
+        self.crf = hasattr(net, 'crf')   # a linear-chain CRF (ops/crf.py) in place of the per-token softmax
+        if self.crf and NT > 64:
+            raise ValueError('TaggerEngine: the CRF kernels take at most 64 tags (got {})'.format(NT))
         self.V, self.E, self.H, self.NT = V, E, H, NT
         self.EP, self.HP, self.NTP = _cdiv(E, 4) * 4, (64 if H <= 64 else 128), _cdiv(NT, 4) * 4
         self.padding_idx = net.emb.padding_idx if net.emb.padding_idx is not None else -1
         HP, EP, NTP = self.HP, self.EP, self.NTP
         shapes = [('emb', (V, EP)), ('w_ih', (2, 4 * HP, EP)), ('w_hh', (2, 4 * HP, HP)), ('b_ih', (2, 4 * HP)),
                   ('b_hh', (2, 4 * HP)), ('w_out', (NTP, 2 * HP)), ('b_out', (NTP,))]
+        if self.crf:
+            shapes += [('crf_trans', (NTP, NTP)), ('crf_start', (NTP,)), ('crf_end', (NTP,))]
         self._seg, o = {}, 0
         for k, sh in shapes:
             self._seg[k] = (o, sh)
@@ -118,6 +132,7 @@ class TaggerEngine:
         self.betas, self.eps = betas, eps
         self.device = dev
         self._graphs, self._inbuf, self._pool = {}, {}, None
+        self._crf_ws = {}                                                # (L, B) -> the CRF kernels' workspace
         self._pinned, self._events, self._flip = [None, None], [None, None], 0
         self.load_module(net)
 
@@ -141,6 +156,10 @@ class TaggerEngine:
             self.seg(self.w, 'b_hh').view(2, 4, HP)[d, :, :H] = getattr(l, 'bias_hh_l0' + suf).float().view(4, H)
         self.seg(self.w, 'w_out').view(self.NTP, 2, HP)[:NT, :, :H] = net.out.weight.float().view(NT, 2, H)
         self.seg(self.w, 'b_out')[:NT] = net.out.bias.float()
+        if self.crf:
+            self.seg(self.w, 'crf_trans')[:NT, :NT] = net.crf.trans.float()
+            self.seg(self.w, 'crf_start')[:NT] = net.crf.start.float()
+            self.seg(self.w, 'crf_end')[:NT] = net.crf.end.float()
 
     def _unpad(self, t: torch.Tensor) -> dict:
         """Module-shaped views (copies) of an arena (weights or gradients)."""
@@ -148,6 +167,9 @@ class TaggerEngine:
         out = {'emb.weight': self.seg(t, 'emb')[:, :E].clone(),
                'out.weight': self.seg(t, 'w_out').view(self.NTP, 2, HP)[:NT, :, :H].reshape(NT, 2 * H).clone(),
                'out.bias': self.seg(t, 'b_out')[:NT].clone()}
+        if self.crf:
+            out.update({'crf.trans': self.seg(t, 'crf_trans')[:NT, :NT], 'crf.start': self.seg(t, 'crf_start')[:NT],
+                        'crf.end': self.seg(t, 'crf_end')[:NT]})
         for d, suf in enumerate(('', '_reverse')):
             out['lstm.weight_ih_l0' + suf] = self.seg(t, 'w_ih').view(2, 4, HP, self.EP)[d, :, :H, :E].reshape(4 * H, E)
             out['lstm.weight_hh_l0' + suf] = self.seg(t, 'w_hh').view(2, 4, HP, HP)[d, :, :H, :H].reshape(4 * H, H)
@@ -198,8 +220,14 @@ class TaggerEngine:
         w_out = self.seg(W, 'w_out')
         logits = S.linear(h2, w_out, self.seg(W, 'b_out'))
         dlog = torch.empty((n, NTP), device=dev, dtype=f)
-        _lib.call("rk_softmax_xent_f32s", _p(logits), NTP, _p(labels), n, self.NT, IGNORE, _p(inv), _p(dlog), NTP,
-                  _p(self.loss_sum), s)
+        if self.crf:   # loss, d(logits) and the three CRF gradients (into the arena, ahead of the clip sum and Adam)
+            _lib.call("rk_crf_nll", _p(logits), _p(self.seg(W, 'crf_trans')), _p(self.seg(W, 'crf_start')),
+                      _p(self.seg(W, 'crf_end')), _p(labels), _p(ib[5 * n + 3:5 * n + 3 + B]), L, B, self.NT, _p(inv),
+                      _p(dlog), _p(self.seg(G, 'crf_trans')), _p(self.seg(G, 'crf_start')), _p(self.seg(G, 'crf_end')),
+                      _p(self.loss_sum), _p(self._crf_workspace(L, B)), s)
+        else:
+            _lib.call("rk_softmax_xent_f32s", _p(logits), NTP, _p(labels), n, self.NT, IGNORE, _p(inv), _p(dlog), NTP,
+                      _p(self.loss_sum), s)
         S.linear_dw(dlog, h2, out=self.seg(G, 'w_out'))
         S.colsum(dlog, self.seg(G, 'b_out'))
         dh = S.linear_dx(dlog, w_out)
@@ -231,6 +259,14 @@ class TaggerEngine:
                 partials, max_norm, stats = self.clip.reduce(self.g)
                 _lib.call("rk_adam_step_clip", *adam, _p(partials), partials.numel(), max_norm, _p(stats), s)
 
+    def _crf_workspace(self, L: int, B: int) -> torch.Tensor:
+        """The CRF kernels' workspace of a batch shape: allocated once per shape (step() asks before any capture)."""
+        ws = self._crf_ws.get((L, B))
+        if ws is None:
+            nbytes = int(_lib.lib().rk_crf_ws_bytes(L, B, self.NT))
+            ws = self._crf_ws[(L, B)] = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=self.device)
+        return ws
+
     def _upload(self, words: np.ndarray, key) -> torch.Tensor:
         """Async copy of a packed batch into the shape's device input buffer (pinned, double-buffered)."""
         k = self._flip
@@ -255,7 +291,9 @@ class TaggerEngine:
         """One training step on a batch-first [B, L] batch (ids int, labels IGNORE-padded)."""
         B, L = x_bl.shape
         key = (L, B)
-        ib = self._upload(pack_batch(x_bl, y_bl, self.padding_idx, self.V), key)
+        # the CRF reads sentence lengths: a sentence's labelled tokens are its first ones
+        lens = (np.asarray(y_bl) != IGNORE).sum(1) if self.crf else None
+        ib = self._upload(pack_batch(x_bl, y_bl, self.padding_idx, self.V, lens), key)
         g = self._graphs.get(key) if graph and update else None
         if g is not None:
             g.replay()
@@ -292,6 +330,25 @@ class TaggerEngine:
     def logits(self, x_bl: np.ndarray) -> torch.Tensor:
         """[B, L, tags] logits (eval: no dropout), eager on the same kernels."""
         B, L = x_bl.shape
+        return self._logits_tm(x_bl).view(L, B, self.NTP)[:, :, :self.NT].transpose(0, 1)
+
+    @torch.no_grad()
+    def decode(self, x_bl: np.ndarray, lens) -> np.ndarray:
+        """[B, L] int32 tags of the CRF's best paths (-1 from lens[b] on): the eval forward, then Viterbi."""
+        if not self.crf:
+            raise RuntimeError('decode needs a net with a crf')
+        B, L = x_bl.shape
+        lg = self._logits_tm(x_bl)
+        dlens = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).to(self.device)
+        tags = torch.empty((B, L), device=self.device, dtype=torch.int32)
+        _lib.call("rk_crf_viterbi", _p(lg), _p(self.seg(self.w, 'crf_trans')), _p(self.seg(self.w, 'crf_start')),
+                  _p(self.seg(self.w, 'crf_end')), _p(dlens), L, B, self.NT, _p(tags), _p(self._crf_workspace(L, B)),
+                  _s())
+        return tags.cpu().numpy()
+
+    def _logits_tm(self, x_bl: np.ndarray) -> torch.Tensor:
+        """[L * B, NTP] logits, time-major rows t * B + b."""
+        B, L = x_bl.shape
         n, HP, EP, dev, s = B * L, self.HP, self.EP, self.device, _s()
         ids = torch.from_numpy(np.ascontiguousarray(x_bl.T, dtype=np.int32).reshape(-1)).to(dev)
         x = torch.empty((n, EP), device=dev, dtype=torch.float32)
@@ -303,8 +360,7 @@ class TaggerEngine:
         gsave = torch.empty((L, B, 2, 4 * HP), device=dev, dtype=torch.float32)
         csave = torch.empty((L, B, 2, HP), device=dev, dtype=torch.float32)
         _lib.call("rk_lstm_fwd32", _p(gin), _p(self.seg(self.w, 'w_hh')), L, B, HP, _p(hout), _p(gsave), _p(csave), s)
-        lg = S.linear(hout.view(n, 2 * HP), self.seg(self.w, 'w_out'), self.seg(self.w, 'b_out'))
-        return lg.view(L, B, self.NTP)[:, :, :self.NT].transpose(0, 1)
+        return S.linear(hout.view(n, 2 * HP), self.seg(self.w, 'w_out'), self.seg(self.w, 'b_out'))
 
     def close(self):
         with graphs.quiesced():

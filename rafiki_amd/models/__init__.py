@@ -10,6 +10,7 @@
   SkDt, SkSvm (sk_models.py)     scikit-learn on CPU
   BigramHmm, PyBiLstm (pos_tagging.py)
   PyBiLstmClip (pos_tagging.py)  PyBiLstm with the gradient-norm cap in the search space
+  PyBiLstmCrf (pos_tagging.py)   PyBiLstm with a linear-chain CRF on top: sentence-level loss, Viterbi decoding
   PgGan (pg_gan.py)              progressive GAN (image generation), data-parallel over RCCL
 """
 import os
@@ -30,6 +31,7 @@ ZOO = {
     'BigramHmm': ('pos_tagging.py', 'POS_TAGGING'),
     'PyBiLstm': ('pos_tagging.py', 'POS_TAGGING'),
     'PyBiLstmClip': ('pos_tagging.py', 'POS_TAGGING'),
+    'PyBiLstmCrf': ('pos_tagging.py', 'POS_TAGGING'),
     'PgGan': ('pg_gan.py', 'IMAGE_GENERATION'),
 }
 

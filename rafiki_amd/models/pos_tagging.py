@@ -11,7 +11,8 @@ length.  On a GPU the BiLSTM's training step and prediction run on the native ta
 the same network runs as torch modules.  ``clip_norm`` (a knob read by PyBiLstm, default 0 = off, and searched by
 PyBiLstmClip) caps the global gradient norm of every step: on the device inside the step's graph on the GPU, by
 torch's clip_grad_norm_ on the CPU; either way the trial logs the epoch's mean and largest norm and the share of
-clipped steps.
+clipped steps.  PyBiLstmCrf puts a linear-chain CRF (ops/crf.py) on the BiLSTM's tag scores: sentence-level loss and
+Viterbi decoding, on the CRF kernels (csrc/kernels/crf.hip) inside the native engine's step on the GPU.
 """
 import math
 
@@ -206,9 +207,19 @@ class PyBiLstm(BaseModel):
         return (self.device.type == 'cuda' and int(self._knobs.get('word_rnn_hidden_size', 64)) <= 128
                 and (self._knobs.get('dtype') or default_dtype()) != 'bf16')
 
+    def _loss(self, logits, y):
+        """The torch path's loss of a batch: logits [B, L, tags], y [B, L] with -100 where no token."""
+        import torch.nn.functional as F
+        return F.cross_entropy(logits.reshape(-1, self._tag_count), y.reshape(-1), ignore_index=-100)
+
+    def _decode(self, eng, x, lens):
+        """[B, L] tags of a batch of ids (numpy, batch-first): on the engine when there is one, else the torch net."""
+        import torch
+        logits = eng.logits(x) if eng is not None else self._net(torch.from_numpy(x).to(self.device))
+        return logits.argmax(-1).cpu().numpy()
+
     def train(self, dataset_uri):
         import torch
-        import torch.nn.functional as F
         ds = dataset_utils.load_dataset_of_corpus(dataset_uri)
         sents = [ds[i] for i in range(len(ds))]
         self._word_dict = {}
@@ -241,8 +252,7 @@ class PyBiLstm(BaseModel):
             n = 0
             norms = []
             for _, x, y in self._batches(ids, tags, int(self._knobs.get('batch_size', 32)), True, rng):
-                logits = self._net(x)
-                loss = F.cross_entropy(logits.reshape(-1, self._tag_count), y.reshape(-1), ignore_index=-100)
+                loss = self._loss(self._net(x), y)
                 opt.zero_grad()
                 loss.backward()
                 if clip is not None:
@@ -331,11 +341,7 @@ class PyBiLstm(BaseModel):
                 eng = self._engine = TaggerEngine(self._net, 0.0, 0.0)
         with torch.no_grad():
             for ch, x, _ in self._batches_np(ids, None, 256, False, None):
-                if eng is not None:
-                    logits = eng.logits(x)
-                else:
-                    logits = self._net(torch.from_numpy(x).to(self.device))
-                pred = logits.argmax(-1).cpu().numpy()
+                pred = self._decode(eng, x, [len(ids[i]) for i in ch])
                 for r, i in enumerate(ch):
                     out[i] = [int(t) for t in pred[r, :len(ids[i])]]
         return out
@@ -369,3 +375,29 @@ class PyBiLstmClip(PyBiLstm):
         cfg = PyBiLstm.get_knob_config()
         cfg['clip_norm'] = FloatKnob(0.25, 8.0, is_exp=True)
         return cfg
+
+
+class PyBiLstmCrf(PyBiLstm):
+    """PyBiLstm with a linear-chain CRF over the output layer's scores (the standard BiLSTM-CRF): trained on the
+    sentence-level negative log-likelihood, decoded with Viterbi.  Same knobs as PyBiLstm.  On the GPU, with up to 64
+    tags, the loss, its gradients and the decoding run on the CRF kernels inside the native engine's step; otherwise
+    (CPU, bf16, more tags) on ops/crf.py in torch."""
+
+    def _create(self):
+        from rafiki_amd.ops.crf import Crf
+        net = super()._create()
+        net.crf = Crf(self._tag_count).to(self.device)
+        return net
+
+    def _native(self) -> bool:
+        return super()._native() and self._tag_count <= 64
+
+    def _loss(self, logits, y):
+        return self._net.crf.nll(logits.float(), y, (y != -100).sum(1))
+
+    def _decode(self, eng, x, lens):
+        import torch
+        if eng is not None:
+            return eng.decode(x, lens)
+        logits = self._net(torch.from_numpy(x).to(self.device))
+        return self._net.crf.decode(logits.float(), lens).cpu().numpy()

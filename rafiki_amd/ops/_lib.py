@@ -132,6 +132,9 @@ _SIGS = {
     "rk_tag_transpose": [vp, vp, i32, i32, i32, vp],
     "rk_tag_add": [vp, vp, vp, i64, vp],
     "rk_softmax_xent_f32s": [vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, vp],
+    # linear-chain CRF on the tagger's logits (crf.hip): loss + all gradients, Viterbi decode
+    "rk_crf_nll": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "rk_crf_viterbi": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp],
     # fused classifier head (head.hip)
     "rk_head_fwd_bwd": [vp, i32, i32, vp, vp, i32, vp, i32, f32, vp, vp, i32, vp, vp, vp, vp],
     "rk_head_fwd_bwd_soft": [vp, i32, i32, vp, vp, i32, vp, vp, vp, f32, i32, f32, vp, vp, i32, vp, vp, vp, vp],
@@ -150,7 +153,7 @@ _SIGS = {
 }
 
 # non-int return types
-_RESTYPES = {"rk_embedding_bwd_ws": (C.c_longlong, [i32])}
+_RESTYPES = {"rk_embedding_bwd_ws": (C.c_longlong, [i32]), "rk_crf_ws_bytes": (C.c_longlong, [i32, i32, i32])}
 
 
 class NativeLibraryError(RuntimeError):

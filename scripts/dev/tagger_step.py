@@ -1,5 +1,6 @@
 """Tagger training-step timing / kernel census (K18): PyBiLstm at E=37, H=51, 45 tags on the native
 engine, batches of 32 sentences bucketed by length.  Prints one JSON line (ms/step, tokens/s).
+``--crf`` times the BiLSTM-CRF step (the CRF loss / gradient kernel in place of the softmax cross-entropy).
 Run under ``rocprofv3 --kernel-trace --stats`` for the step's kernel list."""
 import argparse
 import json
@@ -33,9 +34,14 @@ def main():
     ap.add_argument('--B', type=int, default=32)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--graph', type=int, default=1)
+    ap.add_argument('--crf', action='store_true')
     a = ap.parse_args()
     torch.manual_seed(0)
-    net = Net(a.V, a.E, a.H, a.tags).cuda()
+    net = Net(a.V, a.E, a.H, a.tags)
+    if a.crf:
+        from rafiki_amd.ops.crf import Crf
+        net.crf = Crf(a.tags)
+    net = net.cuda()
     eng = TaggerEngine(net, lr=0.05, dropout=0.1, seed=1)
     rng = np.random.default_rng(0)
     lengths = [8, 12, 16, 20, 24, 28, 32, 40]        # bucket lengths of a PTB-like corpus
@@ -56,7 +62,8 @@ def main():
         toks += x.size
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print(json.dumps({'what': 'tagger_step', 'E': a.E, 'H': a.H, 'tags': a.tags, 'B': a.B, 'graph': a.graph,
+    print(json.dumps({'what': 'tagger_crf_step' if a.crf else 'tagger_step', 'E': a.E, 'H': a.H, 'tags': a.tags,
+                      'B': a.B, 'graph': a.graph,
                       'ms_per_step': round(1e3 * dt / a.steps, 4), 'tokens_per_s': round(toks / dt, 1),
                       'loss': eng.take_loss() / a.steps}))
 
