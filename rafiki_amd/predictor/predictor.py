@@ -166,10 +166,17 @@ class Predictor:
         if r.graphs is not None or r.graphs_failed or os.environ.get('RAFIKI_ENSEMBLE_GRAPH', '1') == '0':
             return r.graphs
         from . import ensemble_graph as EG
-        if not EG.supports([m for _, m in r.models]):
-            r.graphs_failed = True
-            return None
-        r.graphs = EG.EnsembleGraphs([m for _, m in r.models], self.weights)
+        from ..ops.graphs import quiesced
+        # Built once per replica, under the process-wide capture lock.  Requests share a replica, so two threads can
+        # meet it fresh: unlocked, each built an EnsembleGraphs, the second assignment dropped the first one's
+        # captured graphs, and their destructors (and the construction's allocations) ran while another replica's
+        # thread was capturing — which aborts the process (ops/graphs.py).
+        with quiesced():
+            if r.graphs is None and not r.graphs_failed:
+                if EG.supports([m for _, m in r.models]):
+                    r.graphs = EG.EnsembleGraphs([m for _, m in r.models], self.weights)
+                else:
+                    r.graphs_failed = True
         return r.graphs
 
     def _graph_call(self, r, fn):
