@@ -30,6 +30,12 @@ instead: ``crf_trans`` / ``crf_start`` / ``crf_end`` follow ``b_out`` in the are
 the place of the softmax cross-entropy and writes d(logits) and the three CRF gradients, the batch carries its
 sentence lengths, and ``decode`` runs Viterbi on the eval logits.  Without one, the arena layout, the launches and
 the captured graphs are the softmax step's.
+
+A net with a ``gru`` attribute (nn.GRU in place of ``lstm``: PyBiGru, PyBiGruCrf) takes the GRU step: three gate
+blocks [r | z | n] in ``w_ih`` / ``w_hh`` / ``b_ih`` / ``b_hh``, the recurrence on gru.hip.  The candidate gate
+multiplies W_hn h + b_hn by r, so the input projection carries b_ih alone and the kernel adds b_hh; BPTT returns
+two gate-gradient matrices, dgin for W_ih, b_ih and the embedding, dgh for W_hh and b_hh.  Everything else (arena,
+output layer, softmax or CRF loss, clip, Adam, graphs) is shared.
 """
 from __future__ import annotations
 
@@ -91,7 +97,7 @@ def pack_batch(x_bl: np.ndarray, y_bl, padding_idx: int = 0, vocab: Optional[int
 
 
 class TaggerEngine:
-    """Flat padded parameters + Adam state of one PyBiLstm ``Net`` (attributes emb, lstm, out), and its
+    """Flat padded parameters + Adam state of one PyBiLstm ``Net`` (attributes emb, lstm or gru, out), and its
     training step on the in-tree kernels.  ``step`` takes batch-first numpy ids / labels.  ``clip_norm`` (None: off;
     > 0: the cap on the global gradient norm; inf: measure only): one sum-of-squares launch over the gradient arena
     right before the Adam launch, which reads the coefficient on the device — both inside the step's graph."""
@@ -101,9 +107,11 @@ class TaggerEngine:
         dev = net.emb.weight.device
         assert dev.type == 'cuda', 'TaggerEngine runs on the GPU kernels'
         V, E = net.emb.weight.shape
-        H = net.lstm.hidden_size
+        self.gru = hasattr(net, 'gru')   # the GRU cell (gru.hip) in place of the LSTM: three gate blocks
+        cell = net.gru if self.gru else net.lstm
+        H = cell.hidden_size
         NT = net.out.out_features
-        if H > 128 or net.lstm.num_layers != 1 or not net.lstm.bidirectional:
+        if H > 128 or cell.num_layers != 1 or not cell.bidirectional:
             raise ValueError('TaggerEngine: one bidirectional layer of hidden <= 128 (got {})'.format(H))
         self.crf = hasattr(net, 'crf')   # a linear-chain CRF (ops/crf.py) in place of the per-token softmax
         if self.crf and NT > 64:
@@ -112,8 +120,9 @@ class TaggerEngine:
         self.EP, self.HP, self.NTP = _cdiv(E, 4) * 4, (64 if H <= 64 else 128), _cdiv(NT, 4) * 4
         self.padding_idx = net.emb.padding_idx if net.emb.padding_idx is not None else -1
         HP, EP, NTP = self.HP, self.EP, self.NTP
-        shapes = [('emb', (V, EP)), ('w_ih', (2, 4 * HP, EP)), ('w_hh', (2, 4 * HP, HP)), ('b_ih', (2, 4 * HP)),
-                  ('b_hh', (2, 4 * HP)), ('w_out', (NTP, 2 * HP)), ('b_out', (NTP,))]
+        NG = self.NG = 3 if self.gru else 4                              # gate blocks of HP units each
+        shapes = [('emb', (V, EP)), ('w_ih', (2, NG * HP, EP)), ('w_hh', (2, NG * HP, HP)), ('b_ih', (2, NG * HP)),
+                  ('b_hh', (2, NG * HP)), ('w_out', (NTP, 2 * HP)), ('b_out', (NTP,))]
         if self.crf:
             shapes += [('crf_trans', (NTP, NTP)), ('crf_start', (NTP,)), ('crf_end', (NTP,))]
         self._seg, o = {}, 0
@@ -126,8 +135,8 @@ class TaggerEngine:
         self.ctr = torch.zeros(4, device=dev, dtype=torch.int32)       # [0]: steps taken (Adam t, dropout)
         self.loss_sum = torch.zeros(4, **f)                              # [0]: sum of batch-mean losses
         self.clip = None if check_clip_norm(clip_norm) is None else GradClip(self.g, clip_norm)
-        self.whhT = torch.empty((2, HP, 4 * HP), **f)
-        self.bsum = torch.empty(8 * HP, **f)
+        self.whhT = torch.empty((2, HP, NG * HP), **f)
+        self.bsum = None if self.gru else torch.empty(8 * HP, **f)       # the LSTM's b_ih + b_hh
         self.lr, self.p, self.seed = float(lr), float(dropout), int(seed) & ((1 << 63) - 1)
         self.betas, self.eps = betas, eps
         self.device = dev
@@ -143,17 +152,17 @@ class TaggerEngine:
 
     @torch.no_grad()
     def load_module(self, net):
-        E, H, HP, NT = self.E, self.H, self.HP, self.NT
+        E, H, HP, NT, NG = self.E, self.H, self.HP, self.NT, self.NG
         self.w.zero_()
         self.seg(self.w, 'emb')[:, :E] = net.emb.weight.float()
         for d, suf in enumerate(('', '_reverse')):
-            l = net.lstm
-            self.seg(self.w, 'w_ih').view(2, 4, HP, self.EP)[d, :, :H, :E] = \
-                getattr(l, 'weight_ih_l0' + suf).float().view(4, H, E)
-            self.seg(self.w, 'w_hh').view(2, 4, HP, HP)[d, :, :H, :H] = \
-                getattr(l, 'weight_hh_l0' + suf).float().view(4, H, H)
-            self.seg(self.w, 'b_ih').view(2, 4, HP)[d, :, :H] = getattr(l, 'bias_ih_l0' + suf).float().view(4, H)
-            self.seg(self.w, 'b_hh').view(2, 4, HP)[d, :, :H] = getattr(l, 'bias_hh_l0' + suf).float().view(4, H)
+            l = net.gru if self.gru else net.lstm
+            self.seg(self.w, 'w_ih').view(2, NG, HP, self.EP)[d, :, :H, :E] = \
+                getattr(l, 'weight_ih_l0' + suf).float().view(NG, H, E)
+            self.seg(self.w, 'w_hh').view(2, NG, HP, HP)[d, :, :H, :H] = \
+                getattr(l, 'weight_hh_l0' + suf).float().view(NG, H, H)
+            self.seg(self.w, 'b_ih').view(2, NG, HP)[d, :, :H] = getattr(l, 'bias_ih_l0' + suf).float().view(NG, H)
+            self.seg(self.w, 'b_hh').view(2, NG, HP)[d, :, :H] = getattr(l, 'bias_hh_l0' + suf).float().view(NG, H)
         self.seg(self.w, 'w_out').view(self.NTP, 2, HP)[:NT, :, :H] = net.out.weight.float().view(NT, 2, H)
         self.seg(self.w, 'b_out')[:NT] = net.out.bias.float()
         if self.crf:
@@ -163,7 +172,8 @@ class TaggerEngine:
 
     def _unpad(self, t: torch.Tensor) -> dict:
         """Module-shaped views (copies) of an arena (weights or gradients)."""
-        E, H, HP, NT = self.E, self.H, self.HP, self.NT
+        E, H, HP, NT, NG = self.E, self.H, self.HP, self.NT, self.NG
+        cell = 'gru.' if self.gru else 'lstm.'
         out = {'emb.weight': self.seg(t, 'emb')[:, :E].clone(),
                'out.weight': self.seg(t, 'w_out').view(self.NTP, 2, HP)[:NT, :, :H].reshape(NT, 2 * H).clone(),
                'out.bias': self.seg(t, 'b_out')[:NT].clone()}
@@ -171,10 +181,11 @@ class TaggerEngine:
             out.update({'crf.trans': self.seg(t, 'crf_trans')[:NT, :NT], 'crf.start': self.seg(t, 'crf_start')[:NT],
                         'crf.end': self.seg(t, 'crf_end')[:NT]})
         for d, suf in enumerate(('', '_reverse')):
-            out['lstm.weight_ih_l0' + suf] = self.seg(t, 'w_ih').view(2, 4, HP, self.EP)[d, :, :H, :E].reshape(4 * H, E)
-            out['lstm.weight_hh_l0' + suf] = self.seg(t, 'w_hh').view(2, 4, HP, HP)[d, :, :H, :H].reshape(4 * H, H)
-            out['lstm.bias_ih_l0' + suf] = self.seg(t, 'b_ih').view(2, 4, HP)[d, :, :H].reshape(4 * H)
-            out['lstm.bias_hh_l0' + suf] = self.seg(t, 'b_hh').view(2, 4, HP)[d, :, :H].reshape(4 * H)
+            out[cell + 'weight_ih_l0' + suf] = \
+                self.seg(t, 'w_ih').view(2, NG, HP, self.EP)[d, :, :H, :E].reshape(NG * H, E)
+            out[cell + 'weight_hh_l0' + suf] = self.seg(t, 'w_hh').view(2, NG, HP, HP)[d, :, :H, :H].reshape(NG * H, H)
+            out[cell + 'bias_ih_l0' + suf] = self.seg(t, 'b_ih').view(2, NG, HP)[d, :, :H].reshape(NG * H)
+            out[cell + 'bias_hh_l0' + suf] = self.seg(t, 'b_hh').view(2, NG, HP)[d, :, :H].reshape(NG * H)
         return {k: v.clone() for k, v in out.items()}
 
     @torch.no_grad()
@@ -209,13 +220,8 @@ class TaggerEngine:
         _lib.call("rk_tag_embed_fwd", _p(ids), _p(self.seg(W, 'emb')), _p(x), _p(mask), n, EP, self.V, self.p,
                   self.seed, _DROP_STREAM, _p(self.ctr), s)
         self.last_mask = mask   # (tests: the dropout multipliers of the latest eager step, time-major rows)
-        _lib.call("rk_tag_add", _p(self.seg(W, 'b_ih')), _p(self.seg(W, 'b_hh')), _p(self.bsum), 8 * HP, s)
-        w_ih = self.seg(W, 'w_ih').view(8 * HP, EP)
-        gin = S.linear(x, w_ih, self.bsum)
-        hout = torch.empty((L, B, 2, HP), device=dev, dtype=f)
-        gsave = torch.empty((L, B, 2, 4 * HP), device=dev, dtype=f)
-        csave = torch.empty((L, B, 2, HP), device=dev, dtype=f)
-        _lib.call("rk_lstm_fwd32", _p(gin), _p(self.seg(W, 'w_hh')), L, B, HP, _p(hout), _p(gsave), _p(csave), s)
+        w_ih = self.seg(W, 'w_ih').view(2 * self.NG * HP, EP)
+        hout, saved = self._recurrence_fwd(x, L, B)
         h2 = hout.view(n, 2 * HP)
         w_out = self.seg(W, 'w_out')
         logits = S.linear(h2, w_out, self.seg(W, 'b_out'))
@@ -231,19 +237,29 @@ class TaggerEngine:
         S.linear_dw(dlog, h2, out=self.seg(G, 'w_out'))
         S.colsum(dlog, self.seg(G, 'b_out'))
         dh = S.linear_dx(dlog, w_out)
-        _lib.call("rk_tag_transpose", _p(self.seg(W, 'w_hh')), _p(self.whhT), 2, 4 * HP, HP, s)
-        dg = torch.empty((L, B, 2, 4 * HP), device=dev, dtype=f)
-        _lib.call("rk_lstm_bwd32", _p(self.whhT), L, B, HP, _p(dh), _p(gsave), _p(csave), _p(dg), s)
-        dg2 = dg.view(n, 8 * HP)
-        S.linear_dw(dg2, x, out=self.seg(G, 'w_ih').view(8 * HP, EP))
+        GH = self.NG * HP
+        _lib.call("rk_tag_transpose", _p(self.seg(W, 'w_hh')), _p(self.whhT), 2, GH, HP, s)
+        dg = torch.empty((L, B, 2, GH), device=dev, dtype=f)       # d(gin): W_ih, b_ih, the embedding
+        if self.gru:   # and d(W_hh h + b_hh), which differs in the candidate block (da_n * r)
+            dgh = torch.empty((L, B, 2, GH), device=dev, dtype=f)
+            _lib.call("rk_gru_bwd32", _p(self.whhT), L, B, HP, _p(dh), _p(hout), _p(saved[0]), _p(saved[1]), _p(dg),
+                      _p(dgh), s)
+        else:
+            dgh = dg
+            _lib.call("rk_lstm_bwd32", _p(self.whhT), L, B, HP, _p(dh), _p(saved[0]), _p(saved[1]), _p(dg), s)
+        dg2, dgh2 = dg.view(n, 2 * GH), dgh.view(n, 2 * GH)
+        S.linear_dw(dg2, x, out=self.seg(G, 'w_ih').view(2 * GH, EP))
         g_hh = self.seg(G, 'w_hh')
         if L > 1:   # h_{t-1} of the forward direction, h_{t+1} of the reverse one (zero initial state)
-            S.linear_dw(dg2[B:, :4 * HP], h2[:-B, :HP], out=g_hh[0])
-            S.linear_dw(dg2[:-B, 4 * HP:], h2[B:, HP:], out=g_hh[1])
+            S.linear_dw(dgh2[B:, :GH], h2[:-B, :HP], out=g_hh[0])
+            S.linear_dw(dgh2[:-B, GH:], h2[B:, HP:], out=g_hh[1])
         else:
             _lib.call("rk_zero32", _p(g_hh), g_hh.numel(), s)
         S.colsum(dg2, self.seg(G, 'b_ih').view(-1))
-        _lib.call("rk_tag_add", _p(self.seg(G, 'b_ih')), None, _p(self.seg(G, 'b_hh')), 8 * HP, s)
+        if self.gru:
+            S.colsum(dgh2, self.seg(G, 'b_hh').view(-1))
+        else:
+            _lib.call("rk_tag_add", _p(self.seg(G, 'b_ih')), None, _p(self.seg(G, 'b_hh')), 8 * HP, s)
         gx = S.linear_dx(dg2, w_ih)
         g_emb = self.seg(G, 'emb')
         _lib.call("rk_zero32", _p(g_emb), g_emb.numel(), s)
@@ -258,6 +274,26 @@ class TaggerEngine:
             else:
                 partials, max_norm, stats = self.clip.reduce(self.g)
                 _lib.call("rk_adam_step_clip", *adam, _p(partials), partials.numel(), max_norm, _p(stats), s)
+
+    def _recurrence_fwd(self, x: torch.Tensor, L: int, B: int):
+        """Input projection and the recurrence of x [L * B, EP] (time-major rows): hout [L, B, 2, HP] and the two
+        tensors the BPTT kernel reads back (LSTM: gates, cell states; GRU: gates, W_hn h + b_hn)."""
+        HP, W, s = self.HP, self.w, _s()
+        f = dict(device=self.device, dtype=torch.float32)
+        GH = self.NG * HP
+        w_ih = self.seg(W, 'w_ih').view(2 * GH, self.EP)
+        hout = torch.empty((L, B, 2, HP), **f)
+        gsave = torch.empty((L, B, 2, GH), **f)
+        aux = torch.empty((L, B, 2, HP), **f)
+        if self.gru:   # b_hh goes to the kernel: its candidate block sits inside the product with r
+            gin = S.linear(x, w_ih, self.seg(W, 'b_ih').view(-1))
+            _lib.call("rk_gru_fwd32", _p(gin), _p(self.seg(W, 'w_hh')), _p(self.seg(W, 'b_hh')), L, B, HP, _p(hout),
+                      _p(gsave), _p(aux), s)
+        else:
+            _lib.call("rk_tag_add", _p(self.seg(W, 'b_ih')), _p(self.seg(W, 'b_hh')), _p(self.bsum), 8 * HP, s)
+            gin = S.linear(x, w_ih, self.bsum)
+            _lib.call("rk_lstm_fwd32", _p(gin), _p(self.seg(W, 'w_hh')), L, B, HP, _p(hout), _p(gsave), _p(aux), s)
+        return hout, (gsave, aux)
 
     def _crf_workspace(self, L: int, B: int) -> torch.Tensor:
         """The CRF kernels' workspace of a batch shape: allocated once per shape (step() asks before any capture)."""
@@ -354,12 +390,7 @@ class TaggerEngine:
         x = torch.empty((n, EP), device=dev, dtype=torch.float32)
         _lib.call("rk_tag_embed_fwd", _p(ids), _p(self.seg(self.w, 'emb')), _p(x), None, n, EP, self.V, 0.0, 0, 0,
                   None, s)
-        _lib.call("rk_tag_add", _p(self.seg(self.w, 'b_ih')), _p(self.seg(self.w, 'b_hh')), _p(self.bsum), 8 * HP, s)
-        gin = S.linear(x, self.seg(self.w, 'w_ih').view(8 * HP, EP), self.bsum)
-        hout = torch.empty((L, B, 2, HP), device=dev, dtype=torch.float32)
-        gsave = torch.empty((L, B, 2, 4 * HP), device=dev, dtype=torch.float32)
-        csave = torch.empty((L, B, 2, HP), device=dev, dtype=torch.float32)
-        _lib.call("rk_lstm_fwd32", _p(gin), _p(self.seg(self.w, 'w_hh')), L, B, HP, _p(hout), _p(gsave), _p(csave), s)
+        hout, _ = self._recurrence_fwd(x, L, B)
         return S.linear(hout.view(n, 2 * HP), self.seg(self.w, 'w_out'), self.seg(self.w, 'b_out'))
 
     def close(self):

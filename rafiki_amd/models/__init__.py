@@ -11,7 +11,8 @@
   BigramHmm, PyBiLstm (pos_tagging.py)
   PyBiLstmClip (pos_tagging.py)  PyBiLstm with the gradient-norm cap in the search space
   PyBiLstmCrf (pos_tagging.py)   PyBiLstm with a linear-chain CRF on top: sentence-level loss, Viterbi decoding
-  PgGan (pg_gan.py)              progressive GAN (image generation), data-parallel over RCCL
+  PyBiGru, PyBiGruCrf (pos_tagging.py)  the two taggers with a GRU cell (persistent fp32 GRU recurrence kernels)
+  PgGan (pg_gan.py)            progressive GAN (image generation), data-parallel over RCCL
 """
 import os
 
@@ -32,6 +33,8 @@ ZOO = {
     'PyBiLstm': ('pos_tagging.py', 'POS_TAGGING'),
     'PyBiLstmClip': ('pos_tagging.py', 'POS_TAGGING'),
     'PyBiLstmCrf': ('pos_tagging.py', 'POS_TAGGING'),
+    'PyBiGru': ('pos_tagging.py', 'POS_TAGGING'),
+    'PyBiGruCrf': ('pos_tagging.py', 'POS_TAGGING'),
     'PgGan': ('pg_gan.py', 'IMAGE_GENERATION'),
 }
 

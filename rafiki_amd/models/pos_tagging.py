@@ -13,6 +13,8 @@ PyBiLstmClip) caps the global gradient norm of every step: on the device inside 
 torch's clip_grad_norm_ on the CPU; either way the trial logs the epoch's mean and largest norm and the share of
 clipped steps.  PyBiLstmCrf puts a linear-chain CRF (ops/crf.py) on the BiLSTM's tag scores: sentence-level loss and
 Viterbi decoding, on the CRF kernels (csrc/kernels/crf.hip) inside the native engine's step on the GPU.
+PyBiGru / PyBiGruCrf are the same two taggers with a GRU cell (nn.GRU; on the GPU the persistent fp32 GRU recurrence
+of csrc/kernels/gru.hip inside the same engine step).
 """
 import math
 
@@ -401,3 +403,34 @@ class PyBiLstmCrf(PyBiLstm):
             return eng.decode(x, lens)
         logits = self._net(torch.from_numpy(x).to(self.device))
         return self._net.crf.decode(logits.float(), lens).cpu().numpy()
+
+
+class PyBiGru(PyBiLstm):
+    """PyBiLstm with a GRU cell: Embedding -> Dropout -> BiGRU -> Linear, the same knobs (``clip_norm`` included) and
+    the same saved-params format.  On the GPU in fp32 the training step and prediction run on the native engine with
+    the GRU recurrence kernels (gru.hip); on the CPU, or with the bf16 opt-in (there is no bf16 GRU recurrence), the
+    network runs as torch modules."""
+
+    def _create(self):
+        import torch.nn as nn
+        k = self._knobs
+        V = len(self._word_dict) + 2  # 0 = pad, 1 = unknown
+        E, H = int(k.get('word_embed_dims', 64)), int(k.get('word_rnn_hidden_size', 64))
+
+        class Net(nn.Module):
+            def __init__(s):
+                super().__init__()
+                s.emb = nn.Embedding(V, E, padding_idx=0)
+                s.drop = nn.Dropout(float(k.get('word_dropout', 0.1)))
+                s.gru = nn.GRU(E, H, batch_first=True, bidirectional=True)
+                s.out = nn.Linear(2 * H, self._tag_count)
+
+            def forward(s, x):
+                return s.out(s.gru(s.drop(s.emb(x)))[0])
+
+        return Net().to(self.device)
+
+
+class PyBiGruCrf(PyBiLstmCrf, PyBiGru):
+    """PyBiGru with the linear-chain CRF of PyBiLstmCrf: that class's ``_create`` puts the Crf on the net the next
+    class in line builds, here PyBiGru's, and its loss, decoding and 64-tag rule apply unchanged."""

@@ -80,6 +80,9 @@ _SIGS = {
     "rk_lstm_bwd": [vp, i32, i32, i32, vp, vp, vp, vp, vp],
     "rk_lstm_fwd32": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "rk_lstm_bwd32": [vp, i32, i32, i32, vp, vp, vp, vp, vp],
+    # persistent fp32 GRU recurrence (gru.hip): the kernel takes b_hh; BPTT writes dgin and dgh
+    "rk_gru_fwd32": [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp],
+    "rk_gru_bwd32": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
     "rk_wino_weights": [vp, vp, vp, i32, i32, vp],
     "rk_wino_conv_grp": [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, vp],
     "rk_wino_wgrad": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],

@@ -1,6 +1,7 @@
 """Tagger training-step timing / kernel census (K18): PyBiLstm at E=37, H=51, 45 tags on the native
 engine, batches of 32 sentences bucketed by length.  Prints one JSON line (ms/step, tokens/s).
-``--crf`` times the BiLSTM-CRF step (the CRF loss / gradient kernel in place of the softmax cross-entropy).
+``--crf`` times the BiLSTM-CRF step (the CRF loss / gradient kernel in place of the softmax cross-entropy),
+``--gru`` the PyBiGru step (nn.GRU in place of nn.LSTM: the GRU recurrence kernels).
 Run under ``rocprofv3 --kernel-trace --stats`` for the step's kernel list."""
 import argparse
 import json
@@ -18,10 +19,13 @@ from rafiki_amd.engine.tagger import TaggerEngine
 
 
 class Net(torch.nn.Module):
-    def __init__(self, V, E, H, NT):
+    def __init__(self, V, E, H, NT, gru=False):
         super().__init__()
         self.emb = torch.nn.Embedding(V, E, padding_idx=0)
-        self.lstm = torch.nn.LSTM(E, H, batch_first=True, bidirectional=True)
+        if gru:
+            self.gru = torch.nn.GRU(E, H, batch_first=True, bidirectional=True)
+        else:
+            self.lstm = torch.nn.LSTM(E, H, batch_first=True, bidirectional=True)
         self.out = torch.nn.Linear(2 * H, NT)
 
 
@@ -35,9 +39,10 @@ def main():
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--graph', type=int, default=1)
     ap.add_argument('--crf', action='store_true')
+    ap.add_argument('--gru', action='store_true')
     a = ap.parse_args()
     torch.manual_seed(0)
-    net = Net(a.V, a.E, a.H, a.tags)
+    net = Net(a.V, a.E, a.H, a.tags, a.gru)
     if a.crf:
         from rafiki_amd.ops.crf import Crf
         net.crf = Crf(a.tags)
@@ -62,8 +67,8 @@ def main():
         toks += x.size
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print(json.dumps({'what': 'tagger_crf_step' if a.crf else 'tagger_step', 'E': a.E, 'H': a.H, 'tags': a.tags,
-                      'B': a.B, 'graph': a.graph,
+    print(json.dumps({'what': ('gru_' if a.gru else '') + ('tagger_crf_step' if a.crf else 'tagger_step'),
+                      'E': a.E, 'H': a.H, 'tags': a.tags, 'B': a.B, 'graph': a.graph,
                       'ms_per_step': round(1e3 * dt / a.steps, 4), 'tokens_per_s': round(toks / dt, 1),
                       'loss': eng.take_loss() / a.steps}))
 
