@@ -36,6 +36,16 @@ blocks [r | z | n] in ``w_ih`` / ``w_hh`` / ``b_ih`` / ``b_hh``, the recurrence 
 multiplies W_hn h + b_hn by r, so the input projection carries b_ih alone and the kernel adds b_hh; BPTT returns
 two gate-gradient matrices, dgin for W_ih, b_ih and the embedding, dgh for W_hh and b_hh.  Everything else (arena,
 output layer, softmax or CRF loss, clip, Adam, graphs) is shared.
+
+A net with ``char_emb`` (nn.Embedding(CV, Ec, padding_idx=0)) and ``char_conv`` (nn.Conv1d(Ec, F, 3, padding=1)) takes
+the char step (PyBiLstmChar, PyBiLstmCharCrf; either cell, either loss): every token also carries 16 character ids,
+``rk_charcnn_fwd`` (charcnn.hip) turns them into F word features (gather, width-3 convolution, max over the word's
+positions, bias, dropout from a stream id of its own) and the recurrence's input is [x | xc].  The arena keeps the
+input weights' columns E: as a segment of their own (``w_ihc``), so the word path is untouched: gin = x W_ih^T + b as
+before, plus xc W_ihc^T.  ``char_emb`` (CV, EcP), ``char_w`` (FP, 3, EcP: K contiguous, torch's Conv1d.weight is
+[F][Ec][3]), ``char_b`` and ``w_ihc`` follow the other segments; EcP in {16, 32}, FP a multiple of 16 up to 64.
+``rk_charcnn_bwd`` writes the three char gradients into the gradient arena ahead of the clip sum and Adam.  Without
+the char layers the arena layout, the launches and the graphs are as above.
 """
 from __future__ import annotations
 
@@ -52,20 +62,24 @@ from .flat import GradClip, check_clip_norm
 
 IGNORE = -100
 _DROP_STREAM = 0x7a67   # Philox stream id of the tagger's dropout
+_CHAR_STREAM = 0x6368   # and of the dropout on the char features
+NCHAR = 16              # character ids a token carries (uint8, 0 = padding)
 
 
 def _cdiv(a: int, b: int) -> int:
     return -(-a // b)
 
 
-def pack_batch(x_bl: np.ndarray, y_bl, padding_idx: int = 0, vocab: Optional[int] = None, lens=None) -> np.ndarray:
+def pack_batch(x_bl: np.ndarray, y_bl, padding_idx: int = 0, vocab: Optional[int] = None, lens=None,
+               chars=None) -> np.ndarray:
     """One batch as the int32 words the step reads: x_bl / y_bl are [B, L] (batch-first, like the
     reference's batches; labels IGNORE where no token).  Layout, with n = L*B tokens in time-major
     order (t, b): [ids n | labels n | perm n | run ids n | run starts n+1 | #runs | 1/#labelled as
     float bits].  perm is the stable argsort of the ids; run u covers perm[start[u]:start[u+1]] and
     has id uniq[u] (-1 for the padding id: no gradient).  With ``vocab``, ids outside [0, vocab) become
     the padding id, as the forward's gather treats them (no gradient row is written for them).  With ``lens``
-    ([B] sentence lengths, read by the CRF step) B more words follow; without, the layout is as above."""
+    ([B] sentence lengths, read by the CRF step) B more words follow; with ``chars`` ([B, L, 16] uint8 character ids,
+    read by the char step) n * 4 more, the ids time-major [n][16]; without either, the layout is as above."""
     B, L = x_bl.shape
     n = B * L
     ids = np.ascontiguousarray(x_bl.T, dtype=np.int32).reshape(-1)
@@ -83,7 +97,8 @@ def pack_batch(x_bl: np.ndarray, y_bl, padding_idx: int = 0, vocab: Optional[int
     uniq[uniq == padding_idx] = -1
     U = len(uniq)
     cnt = int((labels != IGNORE).sum())
-    out = np.zeros(5 * n + 3 + (0 if lens is None else B), np.int32)
+    nl = 0 if lens is None else B
+    out = np.zeros(5 * n + 3 + nl + (0 if chars is None else 4 * n), np.int32)
     out[0:n] = ids
     out[n:2 * n] = labels
     out[2 * n:3 * n] = perm
@@ -92,8 +107,18 @@ def pack_batch(x_bl: np.ndarray, y_bl, padding_idx: int = 0, vocab: Optional[int
     out[5 * n + 1] = U
     out[5 * n + 2:5 * n + 3] = np.array([1.0 / max(1, cnt)], np.float32).view(np.int32)
     if lens is not None:
-        out[5 * n + 3:] = lens
+        out[5 * n + 3:5 * n + 3 + B] = lens
+    if chars is not None:
+        out[5 * n + 3 + nl:] = _chars_tm(chars, B, L).view(np.int32)
     return out
+
+
+def _chars_tm(chars, B: int, L: int) -> np.ndarray:
+    """[B, L, 16] uint8 character ids as time-major bytes [L * B * 16]."""
+    c = np.asarray(chars)
+    if c.shape != (B, L, NCHAR) or c.dtype != np.uint8:
+        raise ValueError('chars must be uint8 [B, L, {}] (got {} {})'.format(NCHAR, c.dtype, c.shape))
+    return np.ascontiguousarray(c.transpose(1, 0, 2)).reshape(-1)
 
 
 class TaggerEngine:
@@ -117,6 +142,20 @@ class TaggerEngine:
         if self.crf and NT > 64:
             raise ValueError('TaggerEngine: the CRF kernels take at most 64 tags (got {})'.format(NT))
         self.V, self.E, self.H, self.NT = V, E, H, NT
+        self.char = hasattr(net, 'char_emb')   # character-CNN word features (charcnn.hip) beside the word embedding
+        if self.char:
+            CV, Ec = net.char_emb.weight.shape
+            conv = net.char_conv
+            F = conv.out_channels
+            if conv.kernel_size != (3,) or conv.padding != (1,) or conv.in_channels != Ec or conv.bias is None:
+                raise ValueError('TaggerEngine: char_conv must be Conv1d(Ec, F, 3, padding=1) with a bias')
+            if not (CV <= 256 and Ec <= 32 and F <= 64 and net.char_emb.padding_idx == 0):
+                raise ValueError('TaggerEngine: the char kernels take <= 256 characters, Ec <= 32, F <= 64, '
+                                 'padding_idx 0 (got {}, {}, {})'.format(CV, Ec, F))
+            if cell.input_size != E + F:
+                raise ValueError('TaggerEngine: the cell\'s input must be [word | char] features')
+            self.CV, self.Ec, self.F = CV, Ec, F
+            self.EcP, self.FP = (16 if Ec <= 16 else 32), _cdiv(F, 16) * 16
         self.EP, self.HP, self.NTP = _cdiv(E, 4) * 4, (64 if H <= 64 else 128), _cdiv(NT, 4) * 4
         self.padding_idx = net.emb.padding_idx if net.emb.padding_idx is not None else -1
         HP, EP, NTP = self.HP, self.EP, self.NTP
@@ -125,6 +164,9 @@ class TaggerEngine:
                   ('b_hh', (2, NG * HP)), ('w_out', (NTP, 2 * HP)), ('b_out', (NTP,))]
         if self.crf:
             shapes += [('crf_trans', (NTP, NTP)), ('crf_start', (NTP,)), ('crf_end', (NTP,))]
+        if self.char:
+            shapes += [('char_emb', (self.CV, self.EcP)), ('char_w', (self.FP, 3, self.EcP)), ('char_b', (self.FP,)),
+                       ('w_ihc', (2, NG * HP, self.FP))]
         self._seg, o = {}, 0
         for k, sh in shapes:
             self._seg[k] = (o, sh)
@@ -142,6 +184,7 @@ class TaggerEngine:
         self.device = dev
         self._graphs, self._inbuf, self._pool = {}, {}, None
         self._crf_ws = {}                                                # (L, B) -> the CRF kernels' workspace
+        self._char_ws = {}                                               # (L, B) -> rk_charcnn_bwd's workspace
         self._pinned, self._events, self._flip = [None, None], [None, None], 0
         self.load_module(net)
 
@@ -157,8 +200,11 @@ class TaggerEngine:
         self.seg(self.w, 'emb')[:, :E] = net.emb.weight.float()
         for d, suf in enumerate(('', '_reverse')):
             l = net.gru if self.gru else net.lstm
-            self.seg(self.w, 'w_ih').view(2, NG, HP, self.EP)[d, :, :H, :E] = \
-                getattr(l, 'weight_ih_l0' + suf).float().view(NG, H, E)
+            w_ih = getattr(l, 'weight_ih_l0' + suf).float()
+            self.seg(self.w, 'w_ih').view(2, NG, HP, self.EP)[d, :, :H, :E] = w_ih[:, :E].reshape(NG, H, E)
+            if self.char:   # the columns E: multiply the char features
+                self.seg(self.w, 'w_ihc').view(2, NG, HP, self.FP)[d, :, :H, :self.F] = \
+                    w_ih[:, E:].reshape(NG, H, self.F)
             self.seg(self.w, 'w_hh').view(2, NG, HP, HP)[d, :, :H, :H] = \
                 getattr(l, 'weight_hh_l0' + suf).float().view(NG, H, H)
             self.seg(self.w, 'b_ih').view(2, NG, HP)[d, :, :H] = getattr(l, 'bias_ih_l0' + suf).float().view(NG, H)
@@ -169,6 +215,11 @@ class TaggerEngine:
             self.seg(self.w, 'crf_trans')[:NT, :NT] = net.crf.trans.float()
             self.seg(self.w, 'crf_start')[:NT] = net.crf.start.float()
             self.seg(self.w, 'crf_end')[:NT] = net.crf.end.float()
+        if self.char:
+            Ec, F = self.Ec, self.F
+            self.seg(self.w, 'char_emb')[:, :Ec] = net.char_emb.weight.float()
+            self.seg(self.w, 'char_w')[:F, :, :Ec] = net.char_conv.weight.float().permute(0, 2, 1)   # [F][Ec][3]
+            self.seg(self.w, 'char_b')[:F] = net.char_conv.bias.float()
 
     def _unpad(self, t: torch.Tensor) -> dict:
         """Module-shaped views (copies) of an arena (weights or gradients)."""
@@ -180,13 +231,21 @@ class TaggerEngine:
         if self.crf:
             out.update({'crf.trans': self.seg(t, 'crf_trans')[:NT, :NT], 'crf.start': self.seg(t, 'crf_start')[:NT],
                         'crf.end': self.seg(t, 'crf_end')[:NT]})
+        if self.char:
+            Ec, F = self.Ec, self.F
+            out.update({'char_emb.weight': self.seg(t, 'char_emb')[:, :Ec],
+                        'char_conv.weight': self.seg(t, 'char_w')[:F, :, :Ec].permute(0, 2, 1),
+                        'char_conv.bias': self.seg(t, 'char_b')[:F]})
         for d, suf in enumerate(('', '_reverse')):
-            out[cell + 'weight_ih_l0' + suf] = \
-                self.seg(t, 'w_ih').view(2, NG, HP, self.EP)[d, :, :H, :E].reshape(NG * H, E)
+            w_ih = self.seg(t, 'w_ih').view(2, NG, HP, self.EP)[d, :, :H, :E].reshape(NG * H, E)
+            if self.char:
+                w_ihc = self.seg(t, 'w_ihc').view(2, NG, HP, self.FP)[d, :, :H, :self.F].reshape(NG * H, self.F)
+                w_ih = torch.cat([w_ih, w_ihc], 1)
+            out[cell + 'weight_ih_l0' + suf] = w_ih
             out[cell + 'weight_hh_l0' + suf] = self.seg(t, 'w_hh').view(2, NG, HP, HP)[d, :, :H, :H].reshape(NG * H, H)
             out[cell + 'bias_ih_l0' + suf] = self.seg(t, 'b_ih').view(2, NG, HP)[d, :, :H].reshape(NG * H)
             out[cell + 'bias_hh_l0' + suf] = self.seg(t, 'b_hh').view(2, NG, HP)[d, :, :H].reshape(NG * H)
-        return {k: v.clone() for k, v in out.items()}
+        return {k: v.contiguous().clone() for k, v in out.items()}
 
     @torch.no_grad()
     def store_module(self, net):
@@ -221,7 +280,13 @@ class TaggerEngine:
                   self.seed, _DROP_STREAM, _p(self.ctr), s)
         self.last_mask = mask   # (tests: the dropout multipliers of the latest eager step, time-major rows)
         w_ih = self.seg(W, 'w_ih').view(2 * self.NG * HP, EP)
-        hout, saved = self._recurrence_fwd(x, L, B)
+        xc = None
+        if self.char:
+            chars = ib[5 * n + 3 + (B if self.crf else 0):]
+            cmask = torch.empty((n, self.FP), device=dev, dtype=f) if self.p > 0 else None
+            xc, amax = self._char_fwd(chars, n, self.p, self.seed, _CHAR_STREAM, self.ctr, cmask)
+            self.last_char_mask = cmask
+        hout, saved = self._recurrence_fwd(x, L, B, xc)
         h2 = hout.view(n, 2 * HP)
         w_out = self.seg(W, 'w_out')
         logits = S.linear(h2, w_out, self.seg(W, 'b_out'))
@@ -260,6 +325,13 @@ class TaggerEngine:
             S.colsum(dgh2, self.seg(G, 'b_hh').view(-1))
         else:
             _lib.call("rk_tag_add", _p(self.seg(G, 'b_ih')), None, _p(self.seg(G, 'b_hh')), 8 * HP, s)
+        if self.char:   # the char features' share of the input projection, then the fused char backward
+            w_ihc = self.seg(W, 'w_ihc').view(2 * GH, self.FP)
+            S.linear_dw(dg2, xc, out=self.seg(G, 'w_ihc').view(2 * GH, self.FP))
+            gxc = S.linear_dx(dg2, w_ihc)
+            _lib.call("rk_charcnn_bwd", _p(chars), _p(self.seg(W, 'char_emb')), _p(self.seg(W, 'char_w')), _p(gxc),
+                      _p(cmask), _p(amax), n, self.EcP, self.FP, self.CV, _p(self.seg(G, 'char_w')),
+                      _p(self.seg(G, 'char_b')), _p(self.seg(G, 'char_emb')), _p(self._char_workspace(L, B)), s)
         gx = S.linear_dx(dg2, w_ih)
         g_emb = self.seg(G, 'emb')
         _lib.call("rk_zero32", _p(g_emb), g_emb.numel(), s)
@@ -275,9 +347,20 @@ class TaggerEngine:
                 partials, max_norm, stats = self.clip.reduce(self.g)
                 _lib.call("rk_adam_step_clip", *adam, _p(partials), partials.numel(), max_norm, _p(stats), s)
 
-    def _recurrence_fwd(self, x: torch.Tensor, L: int, B: int):
-        """Input projection and the recurrence of x [L * B, EP] (time-major rows): hout [L, B, 2, HP] and the two
-        tensors the BPTT kernel reads back (LSTM: gates, cell states; GRU: gates, W_hn h + b_hn)."""
+    def _char_fwd(self, chars: torch.Tensor, n: int, p: float, seed: int, stream_id: int, ctr, cmask):
+        """xc [n, FP] char features (dropout multipliers into cmask when p > 0) and amax [n, FP] of chars, the
+        device words holding [n][16] uint8 ids."""
+        xc = torch.empty((n, self.FP), device=self.device, dtype=torch.float32)
+        amax = torch.empty((n, self.FP), device=self.device, dtype=torch.int32)
+        _lib.call("rk_charcnn_fwd", _p(chars), _p(self.seg(self.w, 'char_emb')), _p(self.seg(self.w, 'char_w')),
+                  _p(self.seg(self.w, 'char_b')), n, self.EcP, self.FP, self.CV, p, seed, stream_id, _p(ctr), _p(xc),
+                  _p(cmask), _p(amax), _s())
+        return xc, amax
+
+    def _recurrence_fwd(self, x: torch.Tensor, L: int, B: int, xc: Optional[torch.Tensor] = None):
+        """Input projection and the recurrence of x [L * B, EP] (time-major rows; xc [L * B, FP]: the char features
+        beside it): hout [L, B, 2, HP] and the two tensors the BPTT kernel reads back (LSTM: gates, cell states; GRU:
+        gates, W_hn h + b_hn)."""
         HP, W, s = self.HP, self.w, _s()
         f = dict(device=self.device, dtype=torch.float32)
         GH = self.NG * HP
@@ -286,14 +369,33 @@ class TaggerEngine:
         gsave = torch.empty((L, B, 2, GH), **f)
         aux = torch.empty((L, B, 2, HP), **f)
         if self.gru:   # b_hh goes to the kernel: its candidate block sits inside the product with r
-            gin = S.linear(x, w_ih, self.seg(W, 'b_ih').view(-1))
+            gin = self._add_char(S.linear(x, w_ih, self.seg(W, 'b_ih').view(-1)), xc)
             _lib.call("rk_gru_fwd32", _p(gin), _p(self.seg(W, 'w_hh')), _p(self.seg(W, 'b_hh')), L, B, HP, _p(hout),
                       _p(gsave), _p(aux), s)
         else:
             _lib.call("rk_tag_add", _p(self.seg(W, 'b_ih')), _p(self.seg(W, 'b_hh')), _p(self.bsum), 8 * HP, s)
-            gin = S.linear(x, w_ih, self.bsum)
+            gin = self._add_char(S.linear(x, w_ih, self.bsum), xc)
             _lib.call("rk_lstm_fwd32", _p(gin), _p(self.seg(W, 'w_hh')), L, B, HP, _p(hout), _p(gsave), _p(aux), s)
         return hout, (gsave, aux)
+
+    def _add_char(self, gin: torch.Tensor, xc: Optional[torch.Tensor]) -> torch.Tensor:
+        """gin += xc W_ihc^T (S.linear has no accumulate mode: a second GEMM and one elementwise pass)."""
+        if xc is not None:
+            ginc = S.linear(xc, self.seg(self.w, 'w_ihc').view(2 * self.NG * self.HP, self.FP))
+            _lib.call("rk_tag_add", _p(gin), _p(ginc), _p(gin), gin.numel(), _s())
+        return gin
+
+    def _char_workspace(self, L: int, B: int) -> torch.Tensor:
+        """rk_charcnn_bwd's workspace of a batch shape: allocated once per shape (step() asks before any capture)."""
+        ws = self._char_ws.get((L, B))
+        if ws is None:
+            nbytes = int(_lib.lib().rk_charcnn_ws_bytes(L * B, self.EcP, self.FP, self.CV))
+            ws = self._char_ws[(L, B)] = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def _need_chars(self, chars):
+        if (chars is not None) != self.char:
+            raise ValueError('chars ([B, L, 16] uint8) goes with a net that has char_emb / char_conv, and only with one')
 
     def _crf_workspace(self, L: int, B: int) -> torch.Tensor:
         """The CRF kernels' workspace of a batch shape: allocated once per shape (step() asks before any capture)."""
@@ -323,13 +425,17 @@ class TaggerEngine:
         ev.record()
         return dst
 
-    def step(self, x_bl: np.ndarray, y_bl: np.ndarray, update: bool = True, graph: bool = True):
-        """One training step on a batch-first [B, L] batch (ids int, labels IGNORE-padded)."""
+    def step(self, x_bl: np.ndarray, y_bl: np.ndarray, update: bool = True, graph: bool = True, chars=None):
+        """One training step on a batch-first [B, L] batch (ids int, labels IGNORE-padded; chars [B, L, 16] uint8
+        exactly when the net has the char layers)."""
         B, L = x_bl.shape
         key = (L, B)
+        self._need_chars(chars)
+        if self.char:
+            self._char_workspace(L, B)
         # the CRF reads sentence lengths: a sentence's labelled tokens are its first ones
         lens = (np.asarray(y_bl) != IGNORE).sum(1) if self.crf else None
-        ib = self._upload(pack_batch(x_bl, y_bl, self.padding_idx, self.V, lens), key)
+        ib = self._upload(pack_batch(x_bl, y_bl, self.padding_idx, self.V, lens, chars), key)
         g = self._graphs.get(key) if graph and update else None
         if g is not None:
             g.replay()
@@ -363,18 +469,18 @@ class TaggerEngine:
 
     # ------------------------------------------------------------------------ inference
     @torch.no_grad()
-    def logits(self, x_bl: np.ndarray) -> torch.Tensor:
+    def logits(self, x_bl: np.ndarray, chars=None) -> torch.Tensor:
         """[B, L, tags] logits (eval: no dropout), eager on the same kernels."""
         B, L = x_bl.shape
-        return self._logits_tm(x_bl).view(L, B, self.NTP)[:, :, :self.NT].transpose(0, 1)
+        return self._logits_tm(x_bl, chars).view(L, B, self.NTP)[:, :, :self.NT].transpose(0, 1)
 
     @torch.no_grad()
-    def decode(self, x_bl: np.ndarray, lens) -> np.ndarray:
+    def decode(self, x_bl: np.ndarray, lens, chars=None) -> np.ndarray:
         """[B, L] int32 tags of the CRF's best paths (-1 from lens[b] on): the eval forward, then Viterbi."""
         if not self.crf:
             raise RuntimeError('decode needs a net with a crf')
         B, L = x_bl.shape
-        lg = self._logits_tm(x_bl)
+        lg = self._logits_tm(x_bl, chars)
         dlens = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).to(self.device)
         tags = torch.empty((B, L), device=self.device, dtype=torch.int32)
         _lib.call("rk_crf_viterbi", _p(lg), _p(self.seg(self.w, 'crf_trans')), _p(self.seg(self.w, 'crf_start')),
@@ -382,15 +488,19 @@ class TaggerEngine:
                   _s())
         return tags.cpu().numpy()
 
-    def _logits_tm(self, x_bl: np.ndarray) -> torch.Tensor:
+    def _logits_tm(self, x_bl: np.ndarray, chars=None) -> torch.Tensor:
         """[L * B, NTP] logits, time-major rows t * B + b."""
         B, L = x_bl.shape
+        self._need_chars(chars)
         n, HP, EP, dev, s = B * L, self.HP, self.EP, self.device, _s()
         ids = torch.from_numpy(np.ascontiguousarray(x_bl.T, dtype=np.int32).reshape(-1)).to(dev)
         x = torch.empty((n, EP), device=dev, dtype=torch.float32)
         _lib.call("rk_tag_embed_fwd", _p(ids), _p(self.seg(self.w, 'emb')), _p(x), None, n, EP, self.V, 0.0, 0, 0,
                   None, s)
-        hout, _ = self._recurrence_fwd(x, L, B)
+        xc = None
+        if self.char:
+            xc, _ = self._char_fwd(torch.from_numpy(_chars_tm(chars, B, L)).to(dev), n, 0.0, 0, 0, None, None)
+        hout, _ = self._recurrence_fwd(x, L, B, xc)
         return S.linear(hout.view(n, 2 * HP), self.seg(self.w, 'w_out'), self.seg(self.w, 'b_out'))
 
     def close(self):

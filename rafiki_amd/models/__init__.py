@@ -12,6 +12,7 @@
   PyBiLstmClip (pos_tagging.py)  PyBiLstm with the gradient-norm cap in the search space
   PyBiLstmCrf (pos_tagging.py)   PyBiLstm with a linear-chain CRF on top: sentence-level loss, Viterbi decoding
   PyBiGru, PyBiGruCrf (pos_tagging.py)  the two taggers with a GRU cell (persistent fp32 GRU recurrence kernels)
+  PyBiLstmChar, PyBiLstmCharCrf (pos_tagging.py)  PyBiLstm / PyBiLstmCrf with character-CNN word features (charcnn.hip)
   PgGan (pg_gan.py)            progressive GAN (image generation), data-parallel over RCCL
 """
 import os
@@ -35,6 +36,8 @@ ZOO = {
     'PyBiLstmCrf': ('pos_tagging.py', 'POS_TAGGING'),
     'PyBiGru': ('pos_tagging.py', 'POS_TAGGING'),
     'PyBiGruCrf': ('pos_tagging.py', 'POS_TAGGING'),
+    'PyBiLstmChar': ('pos_tagging.py', 'POS_TAGGING'),
+    'PyBiLstmCharCrf': ('pos_tagging.py', 'POS_TAGGING'),
     'PgGan': ('pg_gan.py', 'IMAGE_GENERATION'),
 }
 

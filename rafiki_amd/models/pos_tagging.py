@@ -15,6 +15,10 @@ clipped steps.  PyBiLstmCrf puts a linear-chain CRF (ops/crf.py) on the BiLSTM's
 Viterbi decoding, on the CRF kernels (csrc/kernels/crf.hip) inside the native engine's step on the GPU.
 PyBiGru / PyBiGruCrf are the same two taggers with a GRU cell (nn.GRU; on the GPU the persistent fp32 GRU recurrence
 of csrc/kernels/gru.hip inside the same engine step).
+PyBiLstmChar / PyBiLstmCharCrf add character-level word features (ops/charcnn.py: character embedding -> width-3
+convolution -> max over the word -> dropout, concatenated to the word embedding: BiLSTM-CNN and BiLSTM-CNN-CRF), so a
+word that was not in the training corpus is still read by its spelling; on the GPU the fused kernels of
+csrc/kernels/charcnn.hip inside the same engine step.
 """
 import math
 
@@ -183,6 +187,19 @@ class PyBiLstm(BaseModel):
     def _encode(self, sents_tokens):
         return [[self._word_dict.get(w, 1) for w in s] for s in sents_tokens]
 
+    def _fit_vocab(self, sents):
+        """Vocabularies beyond the word dictionary, from the training sentences (none here)."""
+
+    def _batch_chars(self, ch, L):
+        """[B, L, 16] uint8 character ids of the sentences ``ch`` of the latest _encode; None: a word-only model."""
+        return None
+
+    def _logits(self, ch, x):
+        """The torch net's logits of a batch (x: ids on the device, ch: its sentences' indices)."""
+        import torch
+        c = self._batch_chars(ch, x.shape[1])
+        return self._net(x) if c is None else self._net(x, torch.from_numpy(c).to(self.device))
+
     @staticmethod
     def _batches_np(ids, tags, bs, shuffle, rng):
         order = np.argsort([len(s) for s in ids], kind='stable')  # bucket by length
@@ -214,10 +231,14 @@ class PyBiLstm(BaseModel):
         import torch.nn.functional as F
         return F.cross_entropy(logits.reshape(-1, self._tag_count), y.reshape(-1), ignore_index=-100)
 
-    def _decode(self, eng, x, lens):
-        """[B, L] tags of a batch of ids (numpy, batch-first): on the engine when there is one, else the torch net."""
+    def _decode(self, eng, ch, x, lens):
+        """[B, L] tags of a batch of ids (numpy, batch-first; ch: its sentences' indices): on the engine when there
+        is one, else the torch net."""
         import torch
-        logits = eng.logits(x) if eng is not None else self._net(torch.from_numpy(x).to(self.device))
+        if eng is not None:
+            logits = eng.logits(x, chars=self._batch_chars(ch, x.shape[1]))
+        else:
+            logits = self._logits(ch, torch.from_numpy(x).to(self.device))
         return logits.argmax(-1).cpu().numpy()
 
     def train(self, dataset_uri):
@@ -229,6 +250,7 @@ class PyBiLstm(BaseModel):
             for tok in s:
                 self._word_dict.setdefault(tok[0], len(self._word_dict) + 2)
         self._tag_count = ds.tag_num_classes[0]
+        self._fit_vocab(sents)
         self._net = self._create()
         ids = self._encode([[t[0] for t in s] for s in sents])
         tags = [[t[1] for t in s] for s in sents]
@@ -253,8 +275,8 @@ class PyBiLstm(BaseModel):
             tot = torch.zeros((), device=self.device)
             n = 0
             norms = []
-            for _, x, y in self._batches(ids, tags, int(self._knobs.get('batch_size', 32)), True, rng):
-                loss = self._loss(self._net(x), y)
+            for ch, x, y in self._batches(ids, tags, int(self._knobs.get('batch_size', 32)), True, rng):
+                loss = self._loss(self._logits(ch, x), y)
                 opt.zero_grad()
                 loss.backward()
                 if clip is not None:
@@ -293,8 +315,8 @@ class PyBiLstm(BaseModel):
         eng.take_loss()
         for ep in range(start, epochs):
             n = 0
-            for _, x, y in self._batches_np(ids, tags, bs, True, rng):
-                eng.step(x, y)
+            for ch, x, y in self._batches_np(ids, tags, bs, True, rng):
+                eng.step(x, y, chars=self._batch_chars(ch, x.shape[1]))
                 n += 1
             gs = eng.grad_stats() if eng.clip is not None else None   # before take_loss() restarts them
             logger.log_loss(loss=eng.take_loss() / max(1, n), epoch=ep)   # one host sync per epoch
@@ -343,7 +365,7 @@ class PyBiLstm(BaseModel):
                 eng = self._engine = TaggerEngine(self._net, 0.0, 0.0)
         with torch.no_grad():
             for ch, x, _ in self._batches_np(ids, None, 256, False, None):
-                pred = self._decode(eng, x, [len(ids[i]) for i in ch])
+                pred = self._decode(eng, ch, x, [len(ids[i]) for i in ch])
                 for r, i in enumerate(ch):
                     out[i] = [int(t) for t in pred[r, :len(ids[i])]]
         return out
@@ -397,11 +419,11 @@ class PyBiLstmCrf(PyBiLstm):
     def _loss(self, logits, y):
         return self._net.crf.nll(logits.float(), y, (y != -100).sum(1))
 
-    def _decode(self, eng, x, lens):
+    def _decode(self, eng, ch, x, lens):
         import torch
         if eng is not None:
-            return eng.decode(x, lens)
-        logits = self._net(torch.from_numpy(x).to(self.device))
+            return eng.decode(x, lens, chars=self._batch_chars(ch, x.shape[1]))
+        logits = self._logits(ch, torch.from_numpy(x).to(self.device))
         return self._net.crf.decode(logits.float(), lens).cpu().numpy()
 
 
@@ -434,3 +456,94 @@ class PyBiGru(PyBiLstm):
 class PyBiGruCrf(PyBiLstmCrf, PyBiGru):
     """PyBiGru with the linear-chain CRF of PyBiLstmCrf: that class's ``_create`` puts the Crf on the net the next
     class in line builds, here PyBiGru's, and its loss, decoding and 64-tag rule apply unchanged."""
+
+
+class PyBiLstmChar(PyBiLstm):
+    """PyBiLstm with character-level word features (BiLSTM-CNN, Ma & Hovy 2016): each word's characters go through
+    Embedding(``char_embed_dims``) -> Conv1d(``char_filters``, width 3) -> max over the word, and the LSTM reads
+    [word embedding | char features], ``word_dropout`` on both.  The character vocabulary (0 = pad, 1 = unknown, then
+    the training words' characters by frequency, 256 ids at most) is built in ``train`` and saved with the parameters.
+    On the GPU in fp32 the step and prediction run on the native engine with the fused char kernels (charcnn.hip);
+    on the CPU, with bf16 or a hidden size above 128 the same network runs as torch modules."""
+
+    @staticmethod
+    def get_knob_config():
+        cfg = PyBiLstm.get_knob_config()
+        cfg['char_embed_dims'] = IntegerKnob(8, 32)
+        cfg['char_filters'] = IntegerKnob(16, 64)
+        return cfg
+
+    def __init__(self, **knobs):
+        super().__init__(**knobs)
+        self._char_dict = {}
+        self._char_cache = {}     # word -> its 16 ids
+        self._chars = []          # per sentence of the latest _encode: [len, 16] uint8
+
+    def _char_dims(self):
+        return int(self._knobs.get('char_embed_dims', 25)), int(self._knobs.get('char_filters', 30))
+
+    def _fit_vocab(self, sents):
+        from rafiki_amd.ops.charcnn import build_char_dict
+        self._char_dict = build_char_dict(tok[0] for s in sents for tok in s)
+        self._char_cache = {}
+
+    def _encode(self, sents_tokens):
+        from rafiki_amd.ops.charcnn import NCHAR, encode_word
+        cache = self._char_cache
+        self._chars = []
+        for s in sents_tokens:
+            for w in s:
+                if w not in cache:
+                    cache[w] = encode_word(w, self._char_dict)
+            self._chars.append(np.stack([cache[w] for w in s]) if s else np.zeros((0, NCHAR), np.uint8))
+        return super()._encode(sents_tokens)
+
+    def _batch_chars(self, ch, L):
+        out = np.zeros((len(ch), L, self._chars[0].shape[1] if self._chars else 16), np.uint8)
+        for r, i in enumerate(ch):
+            out[r, :len(self._chars[i])] = self._chars[i]
+        return out
+
+    def _native(self) -> bool:
+        Ec, F = self._char_dims()
+        return super()._native() and Ec <= 32 and F <= 64 and len(self._char_dict) + 2 <= 256
+
+    def _create(self):
+        import torch
+        import torch.nn as nn
+        from rafiki_amd.ops.charcnn import char_features
+        k = self._knobs
+        V, CV = len(self._word_dict) + 2, len(self._char_dict) + 2  # 0 = pad, 1 = unknown
+        E, H = int(k.get('word_embed_dims', 64)), int(k.get('word_rnn_hidden_size', 64))
+        Ec, F = self._char_dims()
+
+        class Net(nn.Module):
+            def __init__(s):
+                super().__init__()
+                s.emb = nn.Embedding(V, E, padding_idx=0)
+                s.char_emb = nn.Embedding(CV, Ec, padding_idx=0)
+                s.char_conv = nn.Conv1d(Ec, F, 3, padding=1)
+                s.drop = nn.Dropout(float(k.get('word_dropout', 0.1)))
+                s.lstm = nn.LSTM(E + F, H, batch_first=True, bidirectional=True)
+                s.out = nn.Linear(2 * H, self._tag_count)
+
+            def forward(s, x, chars):
+                xc = char_features(chars, s.char_emb, s.char_conv)
+                return s.out(s.lstm(torch.cat([s.drop(s.emb(x)), s.drop(xc)], -1))[0])
+
+        return Net().to(self.device)
+
+    def dump_parameters(self):
+        params = super().dump_parameters()
+        params['char_dict'] = self._char_dict
+        return params
+
+    def load_parameters(self, params):
+        self._char_dict = params['char_dict']
+        self._char_cache = {}
+        super().load_parameters(params)
+
+
+class PyBiLstmCharCrf(PyBiLstmCrf, PyBiLstmChar):
+    """The full BiLSTM-CNN-CRF: PyBiLstmChar with the linear-chain CRF of PyBiLstmCrf, composed as PyBiGruCrf is (that
+    class's ``_create`` puts the Crf on the net the next class in line builds, here PyBiLstmChar's)."""

@@ -138,6 +138,9 @@ _SIGS = {
     # linear-chain CRF on the tagger's logits (crf.hip): loss + all gradients, Viterbi decode
     "rk_crf_nll": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "rk_crf_viterbi": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp],
+    # fused character-CNN word features (charcnn.hip): gather + width-3 conv + max + dropout, and its gradients
+    "rk_charcnn_fwd": [vp, vp, vp, vp, i32, i32, i32, i32, f32, C.c_ulonglong, i32, vp, vp, vp, vp, vp],
+    "rk_charcnn_bwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
     # fused classifier head (head.hip)
     "rk_head_fwd_bwd": [vp, i32, i32, vp, vp, i32, vp, i32, f32, vp, vp, i32, vp, vp, vp, vp],
     "rk_head_fwd_bwd_soft": [vp, i32, i32, vp, vp, i32, vp, vp, vp, f32, i32, f32, vp, vp, i32, vp, vp, vp, vp],
@@ -156,7 +159,8 @@ _SIGS = {
 }
 
 # non-int return types
-_RESTYPES = {"rk_embedding_bwd_ws": (C.c_longlong, [i32]), "rk_crf_ws_bytes": (C.c_longlong, [i32, i32, i32])}
+_RESTYPES = {"rk_embedding_bwd_ws": (C.c_longlong, [i32]), "rk_crf_ws_bytes": (C.c_longlong, [i32, i32, i32]),
+             "rk_charcnn_ws_bytes": (C.c_longlong, [i32, i32, i32, i32])}
 
 
 class NativeLibraryError(RuntimeError):
