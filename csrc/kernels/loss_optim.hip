@@ -29,7 +29,14 @@ template <> struct XentSoft<true> {
   float eps;
 };
 
-template <typename DT, bool SOFT>  // d(logits) storage: bf16 (bf16 engine) or float (fp32 engine)
+// PRECISE: expf / logf in place of the fast intrinsics, for the tagger's entry point (rk_softmax_xent_f32s).  With the
+// fast ones the column sum of d(logits) over 17 x 19 tokens (the output layer's bias gradient) erred the same way in
+// all 12 classes, 3.3e-7 of its largest entry against fp64 where fp32 torch is at 8e-8; an error of lse is common to
+// a row's probabilities, so a one-sided one adds up over the rows.  Measured with these: 2.4e-7.
+template <bool PRECISE> RK_DEV float xent_exp(float x) { return PRECISE ? expf(x) : __expf(x); }
+template <bool PRECISE> RK_DEV float xent_log(float x) { return PRECISE ? logf(x) : __logf(x); }
+
+template <typename DT, bool SOFT, bool PRECISE = false>  // d(logits) storage: bf16 (bf16 engine) or float (fp32 engine)
 __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restrict__ logits, int ldl,
                                                            const int* __restrict__ labels, int B, int ncls,
                                                            int ignore_index, float grad_scale,
@@ -56,9 +63,9 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
     if (om > mx || (om == mx && oa < amax)) { mx = om; amax = oa; }
   }
   float se = 0.f;
-  for (int c = lane; c < ncls; c += 64) se += __expf(lr[c] - mx);
+  for (int c = lane; c < ncls; c += 64) se += xent_exp<PRECISE>(lr[c] - mx);
   se = wave_sum(se);
-  const float lse = mx + __logf(se);
+  const float lse = mx + xent_log<PRECISE>(se);
   const int y = labels ? labels[row] : -1;
   bool valid = labels && y != ignore_index && y >= 0 && y < ncls;
   // scale_ptr: a device factor on the gradient and the loss (the tagger's 1 / #valid tokens of a batch,
@@ -83,16 +90,16 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
       if constexpr (SOFT) {
         const float t = (1.f - soft.eps) * (wa * (c == y ? 1.f : 0.f) + wb * (c == y2 ? 1.f : 0.f)) +
                         soft.eps / (float)ncls;
-        if (valid && c < ncls) g = (__expf(lr[c] - lse) - t) * grad_scale;
+        if (valid && c < ncls) g = (xent_exp<PRECISE>(lr[c] - lse) - t) * grad_scale;
       } else {
-        if (valid && c < ncls) g = (__expf(lr[c] - lse) - (c == y ? 1.f : 0.f)) * grad_scale;
+        if (valid && c < ncls) g = (xent_exp<PRECISE>(lr[c] - lse) - (c == y ? 1.f : 0.f)) * grad_scale;
       }
       dr[c] = (DT)g;
     }
   }
   if (probs) {
     float* pr = probs + (long long)row * ncls;
-    for (int c = lane; c < ncls; c += 64) pr[c] = __expf(lr[c] - lse);
+    for (int c = lane; c < ncls; c += 64) pr[c] = xent_exp<PRECISE>(lr[c] - lse);
   }
   if constexpr (SOFT) {
     // loss = lse - (1 - eps) (wa l_ya + wb l_yb) - eps / ncls * sum_c l_c: lane partials in class order, then
@@ -893,7 +900,7 @@ extern "C" int rk_softmax_xent_f32s(const float* logits, int ldl, const int* lab
                                     int ignore_index, const float* scale, float* dlogits, int ldd, float* loss_sum,
                                     void* stream) {
   if (B <= 0) return RK_OK;
-  hipLaunchKernelGGL((softmax_xent_kernel<float, false>), dim3(rk_cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL((softmax_xent_kernel<float, false, true>), dim3(rk_cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream,
                      logits, ldl, labels, B, ncls, ignore_index, 1.0f, dlogits, ldd, nullptr, loss_sum, nullptr,
                      nullptr, scale, XentSoft<false>{});
   RK_LAUNCH_CHECK();

@@ -46,6 +46,17 @@ before, plus xc W_ihc^T.  ``char_emb`` (CV, EcP), ``char_w`` (FP, 3, EcP: K cont
 [F][Ec][3]), ``char_b`` and ``w_ihc`` follow the other segments; EcP in {16, 32}, FP a multiple of 16 up to 64.
 ``rk_charcnn_bwd`` writes the three char gradients into the gradient arena ahead of the clip sum and Adam.  Without
 the char layers the arena layout, the launches and the graphs are as above.
+
+A net with an ``attn`` attribute (ops/attn.py SelfAttention over the 2H recurrent states: PyBiLstmAttn, PyBiLstmAttnCrf;
+either cell, either loss, with or without the char layers) takes the attention step between the recurrence and the
+output layer: qkv = h W_qkv^T + b on ``S.linear``, ``rk_attn_fwd`` (attn.hip: masked softmax(q k^T / sqrt(dh)) v per
+sentence and head, ctx and the log-sum-exp), h' = h + ctx W_o^T + b_o, and the output layer reads h'.  The backward
+takes dh' from the output layer, W_o's gradients and dctx from it, ``rk_attn_bwd`` (d(qkv), P recomputed from the
+log-sum-exp), W_qkv's gradients, and hands dh' + d(qkv) W_qkv to the BPTT kernel.  ``attn_wqkv`` (3 NH DP, 2, HP),
+``attn_bqkv``, ``attn_wo`` (2, HP, NH DP) and ``attn_bo`` follow all other segments, the head dim zero-padded to DP in
+{16, 32}; the batch carries its sentence lengths as for the CRF.  On rows past a sentence's length ctx is zero and the
+engine's h' is h + b_o, where ops/attn.py keeps h: d(logits) is zero there, so the loss and every gradient agree, and
+only ``logits()`` at padded positions differs between the two paths.  Without ``attn`` nothing above changes.
 """
 from __future__ import annotations
 
@@ -78,8 +89,9 @@ def pack_batch(x_bl: np.ndarray, y_bl, padding_idx: int = 0, vocab: Optional[int
     float bits].  perm is the stable argsort of the ids; run u covers perm[start[u]:start[u+1]] and
     has id uniq[u] (-1 for the padding id: no gradient).  With ``vocab``, ids outside [0, vocab) become
     the padding id, as the forward's gather treats them (no gradient row is written for them).  With ``lens``
-    ([B] sentence lengths, read by the CRF step) B more words follow; with ``chars`` ([B, L, 16] uint8 character ids,
-    read by the char step) n * 4 more, the ids time-major [n][16]; without either, the layout is as above."""
+    ([B] sentence lengths, read by the CRF and the attention steps) B more words follow; with ``chars`` ([B, L, 16]
+    uint8 character ids, read by the char step) n * 4 more, the ids time-major [n][16]; without either, the layout is
+    as above."""
     B, L = x_bl.shape
     n = B * L
     ids = np.ascontiguousarray(x_bl.T, dtype=np.int32).reshape(-1)
@@ -156,6 +168,15 @@ class TaggerEngine:
                 raise ValueError('TaggerEngine: the cell\'s input must be [word | char] features')
             self.CV, self.Ec, self.F = CV, Ec, F
             self.EcP, self.FP = (16 if Ec <= 16 else 32), _cdiv(F, 16) * 16
+        self.attn = hasattr(net, 'attn')   # masked multi-head self-attention (attn.hip) ahead of the output layer
+        if self.attn:
+            NH, dh = net.attn.heads, net.attn.head_dims
+            if not (1 <= NH <= 8 and 1 <= dh <= 32):
+                raise ValueError('TaggerEngine: the attention kernels take heads <= 8 and head_dims <= 32 '
+                                 '(got {}, {})'.format(NH, dh))
+            if net.attn.qkv.in_features != 2 * H or net.attn.proj.out_features != 2 * H:
+                raise ValueError('TaggerEngine: attn must read and write the 2H recurrent states')
+            self.NH, self.dh, self.DP = NH, dh, (16 if dh <= 16 else 32)
         self.EP, self.HP, self.NTP = _cdiv(E, 4) * 4, (64 if H <= 64 else 128), _cdiv(NT, 4) * 4
         self.padding_idx = net.emb.padding_idx if net.emb.padding_idx is not None else -1
         HP, EP, NTP = self.HP, self.EP, self.NTP
@@ -167,6 +188,10 @@ class TaggerEngine:
         if self.char:
             shapes += [('char_emb', (self.CV, self.EcP)), ('char_w', (self.FP, 3, self.EcP)), ('char_b', (self.FP,)),
                        ('w_ihc', (2, NG * HP, self.FP))]
+        if self.attn:
+            AD = self.NH * self.DP
+            shapes += [('attn_wqkv', (3 * AD, 2, HP)), ('attn_bqkv', (3 * AD,)), ('attn_wo', (2, HP, AD)),
+                       ('attn_bo', (2, HP))]
         self._seg, o = {}, 0
         for k, sh in shapes:
             self._seg[k] = (o, sh)
@@ -220,6 +245,18 @@ class TaggerEngine:
             self.seg(self.w, 'char_emb')[:, :Ec] = net.char_emb.weight.float()
             self.seg(self.w, 'char_w')[:F, :, :Ec] = net.char_conv.weight.float().permute(0, 2, 1)   # [F][Ec][3]
             self.seg(self.w, 'char_b')[:F] = net.char_conv.bias.float()
+        if self.attn:
+            for k, v in self._attn_views(self.w).items():
+                v.copy_(net.state_dict()[k].float().view(v.shape))
+
+    def _attn_views(self, t: torch.Tensor) -> dict:
+        """The unpadded regions of an arena's attention segments, by the module's parameter names (rows of qkv are
+        (q | k | v, head, d), the 2H states are (direction, unit))."""
+        NH, dh, DP, H, HP = self.NH, self.dh, self.DP, self.H, self.HP
+        return {'attn.qkv.weight': self.seg(t, 'attn_wqkv').view(3, NH, DP, 2, HP)[:, :, :dh, :, :H],
+                'attn.qkv.bias': self.seg(t, 'attn_bqkv').view(3, NH, DP)[:, :, :dh],
+                'attn.proj.weight': self.seg(t, 'attn_wo').view(2, HP, NH, DP)[:, :H, :, :dh],
+                'attn.proj.bias': self.seg(t, 'attn_bo')[:, :H]}
 
     def _unpad(self, t: torch.Tensor) -> dict:
         """Module-shaped views (copies) of an arena (weights or gradients)."""
@@ -236,6 +273,11 @@ class TaggerEngine:
             out.update({'char_emb.weight': self.seg(t, 'char_emb')[:, :Ec],
                         'char_conv.weight': self.seg(t, 'char_w')[:F, :, :Ec].permute(0, 2, 1),
                         'char_conv.bias': self.seg(t, 'char_b')[:F]})
+        if self.attn:
+            AD = self.NH * self.dh
+            shapes = {'attn.qkv.weight': (3 * AD, 2 * H), 'attn.qkv.bias': (3 * AD,), 'attn.proj.weight': (2 * H, AD),
+                      'attn.proj.bias': (2 * H,)}
+            out.update({k: v.reshape(shapes[k]) for k, v in self._attn_views(t).items()})
         for d, suf in enumerate(('', '_reverse')):
             w_ih = self.seg(t, 'w_ih').view(2, NG, HP, self.EP)[d, :, :H, :E].reshape(NG * H, E)
             if self.char:
@@ -282,14 +324,18 @@ class TaggerEngine:
         w_ih = self.seg(W, 'w_ih').view(2 * self.NG * HP, EP)
         xc = None
         if self.char:
-            chars = ib[5 * n + 3 + (B if self.crf else 0):]
+            chars = ib[5 * n + 3 + (B if self.crf or self.attn else 0):]
             cmask = torch.empty((n, self.FP), device=dev, dtype=f) if self.p > 0 else None
             xc, amax = self._char_fwd(chars, n, self.p, self.seed, _CHAR_STREAM, self.ctr, cmask)
             self.last_char_mask = cmask
         hout, saved = self._recurrence_fwd(x, L, B, xc)
         h2 = hout.view(n, 2 * HP)
         w_out = self.seg(W, 'w_out')
-        logits = S.linear(h2, w_out, self.seg(W, 'b_out'))
+        h2a = h2   # what the output layer reads
+        if self.attn:
+            dlens = ib[5 * n + 3:5 * n + 3 + B]
+            h2a, qkv, ctx, lse = self._attn_fwd(h2, dlens, L, B)
+        logits = S.linear(h2a, w_out, self.seg(W, 'b_out'))
         dlog = torch.empty((n, NTP), device=dev, dtype=f)
         if self.crf:   # loss, d(logits) and the three CRF gradients (into the arena, ahead of the clip sum and Adam)
             _lib.call("rk_crf_nll", _p(logits), _p(self.seg(W, 'crf_trans')), _p(self.seg(W, 'crf_start')),
@@ -299,9 +345,21 @@ class TaggerEngine:
         else:
             _lib.call("rk_softmax_xent_f32s", _p(logits), NTP, _p(labels), n, self.NT, IGNORE, _p(inv), _p(dlog), NTP,
                       _p(self.loss_sum), s)
-        S.linear_dw(dlog, h2, out=self.seg(G, 'w_out'))
+        S.linear_dw(dlog, h2a, out=self.seg(G, 'w_out'))
         S.colsum(dlog, self.seg(G, 'b_out'))
         dh = S.linear_dx(dlog, w_out)
+        if self.attn:   # dh is d(h'): the projection's gradients and dctx, the fused backward, then dh += dqkv W_qkv
+            AD = self.NH * self.DP
+            wqkv, wo = self.seg(W, 'attn_wqkv').view(3 * AD, 2 * HP), self.seg(W, 'attn_wo').view(2 * HP, AD)
+            S.linear_dw(dh, ctx, out=self.seg(G, 'attn_wo').view(2 * HP, AD))
+            S.colsum(dh, self.seg(G, 'attn_bo').view(-1))
+            dctx = S.linear_dx(dh, wo)
+            dqkv = torch.empty((n, 3 * AD), device=dev, dtype=f)
+            _lib.call("rk_attn_bwd", _p(qkv), _p(dlens), _p(ctx), _p(lse), _p(dctx), L, B, self.NH, self.DP,
+                      self.dh ** -0.5, _p(dqkv), s)
+            S.linear_dw(dqkv, h2, out=self.seg(G, 'attn_wqkv').view(3 * AD, 2 * HP))
+            S.colsum(dqkv, self.seg(G, 'attn_bqkv'))
+            _lib.call("rk_tag_add", _p(dh), _p(S.linear_dx(dqkv, wqkv)), _p(dh), dh.numel(), s)
         GH = self.NG * HP
         _lib.call("rk_tag_transpose", _p(self.seg(W, 'w_hh')), _p(self.whhT), 2, GH, HP, s)
         dg = torch.empty((L, B, 2, GH), device=dev, dtype=f)       # d(gin): W_ih, b_ih, the embedding
@@ -356,6 +414,18 @@ class TaggerEngine:
                   _p(self.seg(self.w, 'char_b')), n, self.EcP, self.FP, self.CV, p, seed, stream_id, _p(ctr), _p(xc),
                   _p(cmask), _p(amax), _s())
         return xc, amax
+
+    def _attn_fwd(self, h2: torch.Tensor, dlens: torch.Tensor, L: int, B: int):
+        """h2' = h2 + W_o attention(W_qkv h2) of the states h2 [L * B, 2 HP] (dlens: device int32 [B] sentence
+        lengths), and the three tensors the backward reads: qkv [n, 3 NH DP], ctx [n, NH DP], lse [n, NH]."""
+        n, AD, HP, W, s = L * B, self.NH * self.DP, self.HP, self.w, _s()
+        qkv = S.linear(h2, self.seg(W, 'attn_wqkv').view(3 * AD, 2 * HP), self.seg(W, 'attn_bqkv'))
+        ctx = torch.empty((n, AD), device=self.device, dtype=torch.float32)
+        lse = torch.empty((n, self.NH), device=self.device, dtype=torch.float32)
+        _lib.call("rk_attn_fwd", _p(qkv), _p(dlens), L, B, self.NH, self.DP, self.dh ** -0.5, _p(ctx), _p(lse), s)
+        h2a = S.linear(ctx, self.seg(W, 'attn_wo').view(2 * HP, AD), self.seg(W, 'attn_bo').view(-1))
+        _lib.call("rk_tag_add", _p(h2), _p(h2a), _p(h2a), h2a.numel(), s)
+        return h2a, qkv, ctx, lse
 
     def _recurrence_fwd(self, x: torch.Tensor, L: int, B: int, xc: Optional[torch.Tensor] = None):
         """Input projection and the recurrence of x [L * B, EP] (time-major rows; xc [L * B, FP]: the char features
@@ -433,8 +503,8 @@ class TaggerEngine:
         self._need_chars(chars)
         if self.char:
             self._char_workspace(L, B)
-        # the CRF reads sentence lengths: a sentence's labelled tokens are its first ones
-        lens = (np.asarray(y_bl) != IGNORE).sum(1) if self.crf else None
+        # the CRF and the attention read sentence lengths: a sentence's labelled tokens are its first ones
+        lens = (np.asarray(y_bl) != IGNORE).sum(1) if self.crf or self.attn else None
         ib = self._upload(pack_batch(x_bl, y_bl, self.padding_idx, self.V, lens, chars), key)
         g = self._graphs.get(key) if graph and update else None
         if g is not None:
@@ -469,10 +539,11 @@ class TaggerEngine:
 
     # ------------------------------------------------------------------------ inference
     @torch.no_grad()
-    def logits(self, x_bl: np.ndarray, chars=None) -> torch.Tensor:
-        """[B, L, tags] logits (eval: no dropout), eager on the same kernels."""
+    def logits(self, x_bl: np.ndarray, chars=None, lens=None) -> torch.Tensor:
+        """[B, L, tags] logits (eval: no dropout), eager on the same kernels.  lens ([B], read by the attention
+        step): the sentence lengths, by default the count of non-padding ids."""
         B, L = x_bl.shape
-        return self._logits_tm(x_bl, chars).view(L, B, self.NTP)[:, :, :self.NT].transpose(0, 1)
+        return self._logits_tm(x_bl, chars, lens).view(L, B, self.NTP)[:, :, :self.NT].transpose(0, 1)
 
     @torch.no_grad()
     def decode(self, x_bl: np.ndarray, lens, chars=None) -> np.ndarray:
@@ -480,7 +551,7 @@ class TaggerEngine:
         if not self.crf:
             raise RuntimeError('decode needs a net with a crf')
         B, L = x_bl.shape
-        lg = self._logits_tm(x_bl, chars)
+        lg = self._logits_tm(x_bl, chars, lens)
         dlens = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).to(self.device)
         tags = torch.empty((B, L), device=self.device, dtype=torch.int32)
         _lib.call("rk_crf_viterbi", _p(lg), _p(self.seg(self.w, 'crf_trans')), _p(self.seg(self.w, 'crf_start')),
@@ -488,7 +559,7 @@ class TaggerEngine:
                   _s())
         return tags.cpu().numpy()
 
-    def _logits_tm(self, x_bl: np.ndarray, chars=None) -> torch.Tensor:
+    def _logits_tm(self, x_bl: np.ndarray, chars=None, lens=None) -> torch.Tensor:
         """[L * B, NTP] logits, time-major rows t * B + b."""
         B, L = x_bl.shape
         self._need_chars(chars)
@@ -501,7 +572,13 @@ class TaggerEngine:
         if self.char:
             xc, _ = self._char_fwd(torch.from_numpy(_chars_tm(chars, B, L)).to(dev), n, 0.0, 0, 0, None, None)
         hout, _ = self._recurrence_fwd(x, L, B, xc)
-        return S.linear(hout.view(n, 2 * HP), self.seg(self.w, 'w_out'), self.seg(self.w, 'b_out'))
+        h2 = hout.view(n, 2 * HP)
+        if self.attn:
+            if lens is None:
+                lens = (np.asarray(x_bl) != self.padding_idx).sum(1)
+            dlens = torch.from_numpy(np.ascontiguousarray(lens, dtype=np.int32)).to(dev)
+            h2 = self._attn_fwd(h2, dlens, L, B)[0]
+        return S.linear(h2, self.seg(self.w, 'w_out'), self.seg(self.w, 'b_out'))
 
     def close(self):
         with graphs.quiesced():

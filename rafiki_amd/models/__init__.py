@@ -13,6 +13,7 @@
   PyBiLstmCrf (pos_tagging.py)   PyBiLstm with a linear-chain CRF on top: sentence-level loss, Viterbi decoding
   PyBiGru, PyBiGruCrf (pos_tagging.py)  the two taggers with a GRU cell (persistent fp32 GRU recurrence kernels)
   PyBiLstmChar, PyBiLstmCharCrf (pos_tagging.py)  PyBiLstm / PyBiLstmCrf with character-CNN word features (charcnn.hip)
+  PyBiLstmAttn, PyBiLstmAttnCrf (pos_tagging.py)  PyBiLstm / PyBiLstmCrf with masked multi-head self-attention (attn.hip)
   PgGan (pg_gan.py)            progressive GAN (image generation), data-parallel over RCCL
 """
 import os
@@ -38,6 +39,8 @@ ZOO = {
     'PyBiGruCrf': ('pos_tagging.py', 'POS_TAGGING'),
     'PyBiLstmChar': ('pos_tagging.py', 'POS_TAGGING'),
     'PyBiLstmCharCrf': ('pos_tagging.py', 'POS_TAGGING'),
+    'PyBiLstmAttn': ('pos_tagging.py', 'POS_TAGGING'),
+    'PyBiLstmAttnCrf': ('pos_tagging.py', 'POS_TAGGING'),
     'PgGan': ('pg_gan.py', 'IMAGE_GENERATION'),
 }
 

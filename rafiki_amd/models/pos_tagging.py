@@ -19,6 +19,9 @@ PyBiLstmChar / PyBiLstmCharCrf add character-level word features (ops/charcnn.py
 convolution -> max over the word -> dropout, concatenated to the word embedding: BiLSTM-CNN and BiLSTM-CNN-CRF), so a
 word that was not in the training corpus is still read by its spelling; on the GPU the fused kernels of
 csrc/kernels/charcnn.hip inside the same engine step.
+PyBiLstmAttn / PyBiLstmAttnCrf put a masked multi-head self-attention layer (ops/attn.py) between the BiLSTM and the
+output layer (BiLSTM-attention, BiLSTM-attention-CRF); on the GPU the fused kernels of csrc/kernels/attn.hip inside the
+same engine step.
 """
 import math
 
@@ -547,3 +550,51 @@ class PyBiLstmChar(PyBiLstm):
 class PyBiLstmCharCrf(PyBiLstmCrf, PyBiLstmChar):
     """The full BiLSTM-CNN-CRF: PyBiLstmChar with the linear-chain CRF of PyBiLstmCrf, composed as PyBiGruCrf is (that
     class's ``_create`` puts the Crf on the net the next class in line builds, here PyBiLstmChar's)."""
+
+
+class PyBiLstmAttn(PyBiLstm):
+    """PyBiLstm with a masked multi-head self-attention layer (ops/attn.py, residual) between the BiLSTM and the
+    output layer: a token's tag reads every other token's state directly, not only through the recurrence.  Knobs
+    ``attn_heads`` and ``attn_head_dims``; a sentence's length is its count of non-padding ids.  On the GPU in fp32
+    the step and prediction run on the native engine with the fused attention kernels (attn.hip); on the CPU, with
+    bf16 or a hidden size above 128 the same network runs as torch modules."""
+
+    @staticmethod
+    def get_knob_config():
+        cfg = PyBiLstm.get_knob_config()
+        cfg['attn_heads'] = CategoricalKnob([1, 2, 4])
+        cfg['attn_head_dims'] = IntegerKnob(8, 32)
+        return cfg
+
+    def _attn_dims(self):
+        return int(self._knobs.get('attn_heads', 2)), int(self._knobs.get('attn_head_dims', 16))
+
+    def _native(self) -> bool:
+        heads, dh = self._attn_dims()
+        return super()._native() and heads <= 8 and dh <= 32
+
+    def _create(self):
+        import torch.nn as nn
+        from rafiki_amd.ops.attn import SelfAttention
+        k = self._knobs
+        V = len(self._word_dict) + 2  # 0 = pad, 1 = unknown
+        E, H = int(k.get('word_embed_dims', 64)), int(k.get('word_rnn_hidden_size', 64))
+        heads, dh = self._attn_dims()
+
+        class Net(nn.Module):
+            def __init__(s):
+                super().__init__()
+                s.emb = nn.Embedding(V, E, padding_idx=0)
+                s.drop = nn.Dropout(float(k.get('word_dropout', 0.1)))
+                s.lstm = nn.LSTM(E, H, batch_first=True, bidirectional=True)
+                s.attn = SelfAttention(2 * H, heads, dh)
+                s.out = nn.Linear(2 * H, self._tag_count)
+
+            def forward(s, x):
+                return s.out(s.attn(s.lstm(s.drop(s.emb(x)))[0], (x != 0).sum(1)))
+
+        return Net().to(self.device)
+
+
+class PyBiLstmAttnCrf(PyBiLstmCrf, PyBiLstmAttn):
+    """BiLSTM-attention-CRF: PyBiLstmAttn with the linear-chain CRF of PyBiLstmCrf, composed as PyBiGruCrf is."""

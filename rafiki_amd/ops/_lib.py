@@ -141,6 +141,9 @@ _SIGS = {
     # fused character-CNN word features (charcnn.hip): gather + width-3 conv + max + dropout, and its gradients
     "rk_charcnn_fwd": [vp, vp, vp, vp, i32, i32, i32, i32, f32, C.c_ulonglong, i32, vp, vp, vp, vp, vp],
     "rk_charcnn_bwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp],
+    # fused masked multi-head self-attention on the tagger's states (attn.hip): ctx + lse, and d(qkv)
+    "rk_attn_fwd": [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp],
+    "rk_attn_bwd": [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp],
     # fused classifier head (head.hip)
     "rk_head_fwd_bwd": [vp, i32, i32, vp, vp, i32, vp, i32, f32, vp, vp, i32, vp, vp, vp, vp],
     "rk_head_fwd_bwd_soft": [vp, i32, i32, vp, vp, i32, vp, vp, vp, f32, i32, f32, vp, vp, i32, vp, vp, vp, vp],

@@ -2,7 +2,9 @@
 engine, batches of 32 sentences bucketed by length.  Prints one JSON line (ms/step, tokens/s).
 ``--crf`` times the BiLSTM-CRF step (the CRF loss / gradient kernel in place of the softmax cross-entropy),
 ``--gru`` the PyBiGru step (nn.GRU in place of nn.LSTM: the GRU recurrence kernels), ``--char`` the PyBiLstmChar step
-(character-CNN word features beside the word embedding: the charcnn kernels; ``--Ec``, ``--F``, 60 characters).
+(character-CNN word features beside the word embedding: the charcnn kernels; ``--Ec``, ``--F``, 60 characters),
+``--attn`` the PyBiLstmAttn step (masked multi-head self-attention ahead of the output layer: the attn kernels;
+``--heads``, ``--dh``).
 Run under ``rocprofv3 --kernel-trace --stats`` for the step's kernel list."""
 import argparse
 import json
@@ -20,7 +22,7 @@ from rafiki_amd.engine.tagger import TaggerEngine
 
 
 class Net(torch.nn.Module):
-    def __init__(self, V, E, H, NT, gru=False, char=None):
+    def __init__(self, V, E, H, NT, gru=False, char=None, attn=None):
         super().__init__()
         self.emb = torch.nn.Embedding(V, E, padding_idx=0)
         if char:   # (CV, Ec, F)
@@ -31,6 +33,9 @@ class Net(torch.nn.Module):
             self.gru = torch.nn.GRU(E, H, batch_first=True, bidirectional=True)
         else:
             self.lstm = torch.nn.LSTM(E, H, batch_first=True, bidirectional=True)
+        if attn:   # (heads, head dims)
+            from rafiki_amd.ops.attn import SelfAttention
+            self.attn = SelfAttention(2 * H, *attn)
         self.out = torch.nn.Linear(2 * H, NT)
 
 
@@ -48,10 +53,14 @@ def main():
     ap.add_argument('--char', action='store_true')
     ap.add_argument('--Ec', type=int, default=25)
     ap.add_argument('--F', type=int, default=30)
+    ap.add_argument('--attn', action='store_true')
+    ap.add_argument('--heads', type=int, default=2)
+    ap.add_argument('--dh', type=int, default=16)
     a = ap.parse_args()
     torch.manual_seed(0)
     CV = 60
-    net = Net(a.V, a.E, a.H, a.tags, a.gru, (CV, a.Ec, a.F) if a.char else None)
+    net = Net(a.V, a.E, a.H, a.tags, a.gru, (CV, a.Ec, a.F) if a.char else None,
+              (a.heads, a.dh) if a.attn else None)
     if a.crf:
         from rafiki_amd.ops.crf import Crf
         net.crf = Crf(a.tags)
@@ -79,7 +88,7 @@ def main():
         toks += x.size
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print(json.dumps({'what': ('gru_' if a.gru else '') + ('char_' if a.char else '')
+    print(json.dumps({'what': ('gru_' if a.gru else '') + ('char_' if a.char else '') + ('attn_' if a.attn else '')
                       + ('tagger_crf_step' if a.crf else 'tagger_step'),
                       'E': a.E, 'H': a.H, 'tags': a.tags, 'B': a.B, 'graph': a.graph,
                       'ms_per_step': round(1e3 * dt / a.steps, 4), 'tokens_per_s': round(toks / dt, 1),
