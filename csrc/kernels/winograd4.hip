@@ -32,6 +32,7 @@
 //     MFMAs on the 32x32 layers (profiles/wino4_load_breakdown_r5.jsonl).
 #include <type_traits>
 #include "common.h"
+#include <algorithm>
 #include <cstdlib>
 
 namespace {
@@ -1828,127 +1829,152 @@ __global__ __launch_bounds__(256) void w4pt_conv_out_kernel(const float* __restr
 
 // The same with VW-channel vectors (VW = 2: 8-B, 4: 16-B accesses; the scalar kernel's 4-B accesses ran at
 // ~3.2 TB/s): one thread per (tile, VW channels) — 36 vector loads of Y', 16 vector stores, vector gate
-// loads; a 64-thread block = 64 / (64 / VW) tiles x 64 channels, many blocks even on the 4x4 maps.
+// loads.  A 256-thread block covers TPB = 256 / (64 / VW) tiles x 64 channels per step and walks the tile
+// groups gridDim.x / nblk apart (the launcher caps the grid at PT_OUT_CAP blocks).  Statistics: a thread sums
+// the 16 elements of its tile and a wave adds its 64 / LPT tile lanes in fp32 (the partial sums the one-wave
+// blocks of the earlier form sent to the slots, in the same order, so only fp64 additions are regrouped);
+// these stay in fp64 registers across the walk: one fp64 LDS fold and one set of atomics per block.
 template <int VW>
-__global__ __launch_bounds__(64) void w4pt_conv_outv_kernel(const float* __restrict__ yt, float* __restrict__ y,
-                                                            const float* __restrict__ bp, double* stats, int slotMask,
-                                                            const float* __restrict__ gate, int Nb, int H, int W,
-                                                            int N, int TW, int THW, int T, int flags, int nslab,
-                                                            long long slab, long long qs, long long ts,
-                                                            float slope) {
-  constexpr int LPT = 64 / VW, TPB = 64 / LPT;   // lanes per tile, tiles per block
+__global__ __launch_bounds__(256) void w4pt_conv_outv_kernel(const float* __restrict__ yt, float* __restrict__ y,
+                                                             const float* __restrict__ bp, double* stats, int slotMask,
+                                                             const float* __restrict__ gate, int Nb, int H, int W,
+                                                             int N, int TW, int THW, int T, int flags, int nslab,
+                                                             long long slab, long long qs, long long ts,
+                                                             float slope) {
+  constexpr int LPT = 64 / VW, TPB = 256 / LPT;   // lanes per tile, tiles per block and step
+  constexpr int TPW = 64 / LPT;                   // tiles per wave
   typedef __attribute__((ext_vector_type(VW))) float fv;
-  __shared__ float red[2][TPB][64];
+  __shared__ double red[2][4][64];
   const int nblk = (N + 63) / 64;
   const int nb = blockIdx.x % nblk, tb = blockIdx.x / nblk;
+  const int tstep = (gridDim.x / nblk) * TPB;     // the grid is a multiple of nblk
   const int qd = threadIdx.x % LPT, tg = threadIdx.x / LPT;
   const int n = nb * 64 + VW * qd;
   const bool nok = n < N;
   fv bs = {}, sh = {};
   if ((flags & (WF_BIAS | WF_BNB | WF_BNP)) && nok) bs = *(const fv*)(bp + n);
   if ((flags & (WF_BNB | WF_BNP)) && nok) sh = *(const fv*)(bp + N + n);
-  fv s = {}, ss = {};
-  const int t = tb * TPB + tg;
-  if (t < T && nok) {
-    fv m[36];
-    const float* src = yt + (long long)t * ts + n;
+  const int tgw = tg % TPW;                       // this thread's tile lane within its wave
+  double ds[VW] = {}, dss[VW] = {};
+  for (int tw = tb * TPB + tg - tgw; tw < T; tw += tstep) {   // tw, the wave's first tile, is wave-uniform
+    const int t = tw + tgw;
+    fv s = {}, ss = {};
+    if (t < T && nok) {
+      fv m[36];
+      const float* src = yt + (long long)t * ts + n;
 #pragma unroll
-    for (int q = 0; q < 36; ++q) m[q] = *(const fv*)(src + q * qs);
-    for (int k = 1; k < nslab; ++k)   // split-K partial slabs of the GEMM
+      for (int q = 0; q < 36; ++q) m[q] = *(const fv*)(src + q * qs);
+      for (int k = 1; k < nslab; ++k)   // split-K partial slabs of the GEMM
 #pragma unroll
-      for (int q = 0; q < 36; ++q) m[q] += *(const fv*)(src + k * slab + q * qs);
-    const int im = t / THW, rr = t - im * THW, ty = rr / TW;
-    const int oy = 4 * ty, ox = 4 * (rr - ty * TW);
-    fv res[4][4];
+        for (int q = 0; q < 36; ++q) m[q] += *(const fv*)(src + k * slab + q * qs);
+      const int im = t / THW, rr = t - im * THW, ty = rr / TW;
+      const int oy = 4 * ty, ox = 4 * (rr - ty * TW);
+      fv res[4][4];
 #pragma unroll
-    for (int e = 0; e < VW; ++e) {
-      float tt[6][4];
+      for (int e = 0; e < VW; ++e) {
+        float tt[6][4];
 #pragma unroll
-      for (int a = 0; a < 6; ++a) {          // M A: along columns
-        float o[4];
-        at6(m[a * 6 + 0][e], m[a * 6 + 1][e], m[a * 6 + 2][e], m[a * 6 + 3][e], m[a * 6 + 4][e], m[a * 6 + 5][e], o);
+        for (int a = 0; a < 6; ++a) {          // M A: along columns
+          float o[4];
+          at6(m[a * 6 + 0][e], m[a * 6 + 1][e], m[a * 6 + 2][e], m[a * 6 + 3][e], m[a * 6 + 4][e], m[a * 6 + 5][e], o);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) tt[a][j] = o[j];
+          for (int j = 0; j < 4; ++j) tt[a][j] = o[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float o[4];
+          at6(tt[0][j], tt[1][j], tt[2][j], tt[3][j], tt[4][j], tt[5][j], o);   // A^T (M A): along rows
+#pragma unroll
+          for (int i = 0; i < 4; ++i) res[i][j][e] = o[i];
+        }
       }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float o[4];
-        at6(tt[0][j], tt[1][j], tt[2][j], tt[3][j], tt[4][j], tt[5][j], o);   // A^T (M A): along rows
+      for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) res[i][j][e] = o[i];
+        for (int j = 0; j < 4; ++j) {
+          fv v = res[i][j];
+          const long long idx = (((long long)im * H + oy + i) * W + ox + j) * N + n;
+          if (flags & WF_BIAS) v += bs;
+          if (flags & WF_STATS) {
+            s += v;
+            ss += v * v;
+          }
+          if (flags & WF_RELU) {
+#pragma unroll
+            for (int e = 0; e < VW; ++e) v[e] = fmaxf(v[e], 0.f);
+          }
+          if (flags & WF_LRELU) {
+#pragma unroll
+            for (int e = 0; e < VW; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * slope;
+          }
+          if (flags & WF_BNB) {
+            const fv g = *(const fv*)(gate + idx);
+#pragma unroll
+            for (int e = 0; e < VW; ++e) {
+              v[e] = g[e] * bs[e] + sh[e] > 0.f ? v[e] : 0.f;
+              s[e] += v[e];
+              ss[e] += v[e] * g[e];
+            }
+          }
+          if (flags & WF_BNP) {
+            const long long W2 = 2LL * W;
+            const long long q0 = (((long long)im * 2 * H + 2 * (oy + i)) * W2 + 2 * (ox + j)) * N + n;
+            const fv y4[4] = {*(const fv*)(gate + q0), *(const fv*)(gate + q0 + N), *(const fv*)(gate + q0 + W2 * N),
+                              *(const fv*)(gate + q0 + W2 * N + N)};
+#pragma unroll
+            for (int e = 0; e < VW; ++e) {
+              float best = -INFINITY, zb = 0.f, yb = 0.f;
+#pragma unroll
+              for (int w4 = 0; w4 < 4; ++w4) {   // first maximal relu(z) of the window (torch max_pool2d rule)
+                const float z = y4[w4][e] * bs[e] + sh[e];
+                const float av = fmaxf(z, 0.f);
+                if (av > best) { best = av; zb = z; yb = y4[w4][e]; }
+              }
+              const float dz = zb > 0.f ? v[e] : 0.f;
+              s[e] += dz;
+              ss[e] += dz * yb;
+            }
+          }
+          *(fv*)(y + idx) = v;
+        }
+    }
+    if (flags & (WF_STATS | WF_BNB | WF_BNP)) {   // the whole wave is here: tw is wave-uniform
+#pragma unroll
+      for (int e = 0; e < VW; ++e) {
+        float a = 0.f, b = 0.f;
+#pragma unroll
+        for (int r = 0; r < TPW; ++r) {           // the wave's tile lanes in order, fp32
+          a += __shfl(s[e], qd + LPT * r);
+          b += __shfl(ss[e], qd + LPT * r);
+        }
+        ds[e] += (double)a;
+        dss[e] += (double)b;
       }
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        fv v = res[i][j];
-        const long long idx = (((long long)im * H + oy + i) * W + ox + j) * N + n;
-        if (flags & WF_BIAS) v += bs;
-        if (flags & WF_STATS) {
-          s += v;
-          ss += v * v;
-        }
-        if (flags & WF_RELU) {
-#pragma unroll
-          for (int e = 0; e < VW; ++e) v[e] = fmaxf(v[e], 0.f);
-        }
-        if (flags & WF_LRELU) {
-#pragma unroll
-          for (int e = 0; e < VW; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * slope;
-        }
-        if (flags & WF_BNB) {
-          const fv g = *(const fv*)(gate + idx);
-#pragma unroll
-          for (int e = 0; e < VW; ++e) {
-            v[e] = g[e] * bs[e] + sh[e] > 0.f ? v[e] : 0.f;
-            s[e] += v[e];
-            ss[e] += v[e] * g[e];
-          }
-        }
-        if (flags & WF_BNP) {
-          const long long W2 = 2LL * W;
-          const long long q0 = (((long long)im * 2 * H + 2 * (oy + i)) * W2 + 2 * (ox + j)) * N + n;
-          const fv y4[4] = {*(const fv*)(gate + q0), *(const fv*)(gate + q0 + N), *(const fv*)(gate + q0 + W2 * N),
-                            *(const fv*)(gate + q0 + W2 * N + N)};
-#pragma unroll
-          for (int e = 0; e < VW; ++e) {
-            float best = -INFINITY, zb = 0.f, yb = 0.f;
-#pragma unroll
-            for (int w4 = 0; w4 < 4; ++w4) {   // first maximal relu(z) of the window (torch max_pool2d rule)
-              const float z = y4[w4][e] * bs[e] + sh[e];
-              const float av = fmaxf(z, 0.f);
-              if (av > best) { best = av; zb = z; yb = y4[w4][e]; }
-            }
-            const float dz = zb > 0.f ? v[e] : 0.f;
-            s[e] += dz;
-            ss[e] += dz * yb;
-          }
-        }
-        *(fv*)(y + idx) = v;
-      }
   }
   if (flags & (WF_STATS | WF_BNB | WF_BNP)) {
+    if (tgw == 0) {
 #pragma unroll
-    for (int e = 0; e < VW; ++e) {
-      red[0][tg][VW * qd + e] = s[e];
-      red[1][tg][VW * qd + e] = ss[e];
+      for (int e = 0; e < VW; ++e) {
+        red[0][threadIdx.x >> 6][VW * qd + e] = ds[e];
+        red[1][threadIdx.x >> 6][VW * qd + e] = dss[e];
+      }
     }
     __syncthreads();
-    const int c = threadIdx.x;   // 64 threads: one channel of the block's 64 each
-    if (nb * 64 + c < N) {
-      float a = 0.f, b = 0.f;
-#pragma unroll
-      for (int r = 0; r < TPB; ++r) {
-        a += red[0][r][c];
-        b += red[1][r][c];
-      }
+    const int c = threadIdx.x & 63, which = threadIdx.x >> 6;   // 128 threads: one (sum, channel) each
+    if (which < 2 && nb * 64 + c < N) {
+      const double v = (red[which][0][c] + red[which][1][c]) + (red[which][2][c] + red[which][3][c]);
       double* slot = stats + (long long)(blockIdx.x & slotMask) * 2 * N;
-      unsafeAtomicAdd(slot + nb * 64 + c, (double)a);
-      unsafeAtomicAdd(slot + N + nb * 64 + c, (double)b);
+      unsafeAtomicAdd(slot + which * N + nb * 64 + c, v);
     }
   }
 }
+
+// grid cap of w4pt_conv_outv_kernel: two 256-thread blocks per CU of a 256-CU part, which is what fits at
+// VW = 2 (178 VGPRs, two waves per SIMD), so one block's loads are in flight while the other transforms.
+// The VW = 4 form holds 256 VGPRs + 36 AGPRs (one wave per SIMD, one block per CU): a capped grid is two
+// rounds of blocks there.
+constexpr long long PT_OUT_CAP = 512;
 
 }  // namespace
 
@@ -1970,20 +1996,24 @@ extern "C" int rk_wino4_pt_conv_out(const float* yt, float* y, const float* bias
   const long long blocks = ((N + 63) / 64) * ((T + 3) / 4);
   if (nslab > 1 && slab < 36 * T * N) return RK_EBADARG;
   const long long qs = tmajor ? N : T * N, ts = tmajor ? 36LL * N : N;
-  // vector width 2 (8-B accesses, 2 tiles x 64 channels per block) by default; RAFIKI_PT_OUT_VW=4 selects the
-  // 16-B form: -4 us per VGG-small step but +45 us per PG-GAN lod-3 round and +0.23 ms at lod 0 on the same
-  // box (profiles/pt_out_vw_ab_r6.txt)
+  // vector width 2 (8-B accesses, 8 tiles x 64 channels per block and step) by default; RAFIKI_PT_OUT_VW=4
+  // selects the 16-B form: -4 us per VGG-small step but +45 us per PG-GAN lod-3 round and +0.23 ms at lod 0 on
+  // the same box (profiles/pt_out_vw_ab_r6.txt; measured on the earlier one-wave blocks.  As a 256-thread block
+  // the 16-B form fits one block per CU, half of PT_OUT_CAP at a time, and has not been measured again)
   static const int vw = [] {
     const char* e = std::getenv("RAFIKI_PT_OUT_VW");
     return e && std::atoi(e) == 4 ? 4 : 2;
   }();
   if (N % vw == 0) {
-    const long long blocksv = ((N + 63) / 64) * ((T + vw - 1) / vw);   // vw tiles x 64 channels per block
+    // nblk channel blocks x tile groups of 4 vw tiles, the tile groups capped so that the grid stays within
+    // PT_OUT_CAP blocks (a multiple of nblk: every block walks the tile groups of one channel block)
+    const long long nblk = (N + 63) / 64, groups = (T + 4 * vw - 1) / (4 * vw);
+    const long long blocksv = nblk * std::min(groups, std::max(1LL, PT_OUT_CAP / nblk));
     if (vw == 4)
-      hipLaunchKernelGGL(w4pt_conv_outv_kernel<4>, dim3((unsigned)blocksv), dim3(64), 0, (hipStream_t)stream, yt, y,
+      hipLaunchKernelGGL(w4pt_conv_outv_kernel<4>, dim3((unsigned)blocksv), dim3(256), 0, (hipStream_t)stream, yt, y,
                          bias, stats, slotMask, gate, Nb, H, W, N, TW, THW, (int)T, flags, nslab, slab, qs, ts, slope);
     else
-      hipLaunchKernelGGL(w4pt_conv_outv_kernel<2>, dim3((unsigned)blocksv), dim3(64), 0, (hipStream_t)stream, yt, y,
+      hipLaunchKernelGGL(w4pt_conv_outv_kernel<2>, dim3((unsigned)blocksv), dim3(256), 0, (hipStream_t)stream, yt, y,
                          bias, stats, slotMask, gate, Nb, H, W, N, TW, THW, (int)T, flags, nslab, slab, qs, ts, slope);
     RK_LAUNCH_CHECK();
     return RK_OK;
